@@ -13,10 +13,16 @@ window (20 outer iterations, mu 0.1 -> 1.4e-8).  Each instance restarts its solv
 (x0, y0, mu0, Delta0) after every 20 outer iterations (riptrm_options.restart_every), so any
 --warmup/--steps keeps measuring that same workload instead of running into the mu floor.
 
-The JSON line also carries:
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs DIR`` if asked (the x and y
+the last timed step left, DIR/<name>.npy; same arguments, same inputs, so two builds compare output
+for output) and prints the JSON line.  Everything that takes time of its own beside the headline
+figure waits for ``--full``:
 * roofline: the S-pass kernel (k_gemv) timed with HIP events on the stream it runs on, over the
   timed region: algorithmic bytes (8 n^2 + 16 n per instance-pass) / summed kernel time,
-  against the 8 TB/s HBM3E peak; ``traffic`` from a committed rocprofv3 PMC summary if present;
+  against the 8 TB/s HBM3E peak; ``traffic`` from a committed rocprofv3 PMC summary if present
+  (a large batch's timed window carries those events either way, so its plain line has this entry
+  too; small batches replay hipGraphs and are profiled in a second window, the Exact_RepMat
+  eigensolver roofs in launches of their own: --full only);
 * cpu_baseline: the CPU oracle (vectorised NumPy "port") on a bounded sample of the same workload,
   the better of two variants: one instance with all BLAS threads, and --cpu-procs
   single-threaded processes with one instance each, over the same outer-iteration window.
@@ -44,6 +50,25 @@ MFMA_F64_PEAK_TFS = 78.6  # MI355X dense FP64 matrix peak (spec); tools/mfma_ben
 
 def log(msg):
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_MAX_BYTES = 64 * 10 ** 6   # of files on disk, .npy headers included
+NPY_HEADER_ALLOWANCE = 1024     # per file; a version-1 header of these shapes is 128 bytes
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """--dump-outputs: every array as path/<name>.npy in float64, the files at most DUMP_MAX_BYTES in
+    all (each array an equal share, its header's allowance taken off first).  A larger array is cut to a sample of its flattened elements at sorted
+    indices drawn without replacement from RandomState(0): the same elements for the same shape in
+    every run and every build, so two dumps compare element for element."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = max(0, DUMP_MAX_BYTES // max(1, len(arrays)) - NPY_HEADER_ALLOWANCE) // 8
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.size > share:
+            a = a.reshape(-1)[np.sort(np.random.RandomState(0).choice(a.size, share, replace=False))]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 def trs_options(trs: str) -> dict:
@@ -379,6 +404,13 @@ def main():
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL)")
     ap.add_argument("--dump", default="",
                     help="rank 0 writes the gathered x, y and stats of every global instance to this .npz")
+    ap.add_argument("--full", action="store_true",
+                    help="also run everything beside the headline figure: the CPU baselines, the roofline (kernel timings "
+                         "that take a window or launches of their own included) and the per-kernel detail")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps rank 0 writes what the timed path computed in its last step as "
+                         "DIR/<name>.npy (float64; at most 64 MB of files in all, a fixed seeded sample of larger "
+                         "arrays): every global instance for the NonnegPCA lines, rank 0's batch for si and stiefel")
     ap.add_argument("--dist-at-1", action="store_true",
                     help="with --gpus 1: still initialise a (one-rank) process group, so the collectives run")
     ap.add_argument("--same-device", action="store_true",
@@ -386,6 +418,8 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # `python bench.py --gpus N` outside torchrun: launch the N ranks here, before anything
         # touches the GPU (children are started as subprocesses, never exec'd)
@@ -464,11 +498,20 @@ def main():
     if dist.is_initialized():
         dist.barrier()
     st1 = eng.stats()
-    if graph_mode:
+    # kernels are timed inside the window (large batch) or, with --full, in a second window
+    timed = args.full or not graph_mode
+    # the state the timed window's last step left (a further profiled window moves it on)
+    res = eng.result() if (args.dump_outputs or args.dump or dist.is_initialized()) else None
+    res_timed = res
+    if not timed:
+        prof = {"gemv_ms": 0.0, "gemv_launches": 0, "state_ms": 0.0, "state_launches": 0}
+    elif graph_mode:
         engine.profile_enable(eng, True)
         eng.run_until(W + 2 * K)
         prof = engine.profile_read(eng)
         st_p = eng.stats()
+        if res is not None:
+            res = eng.result()   # --dump and the final gather report the state after this window, as before
         passes_prof = float((st_p[:, engine.C["RIPTRM_STAT_PASSES"]] - st1[:, engine.C["RIPTRM_STAT_PASSES"]]).sum())
         rhs_prof = float((st_p[:, engine.C["RIPTRM_STAT_RHS"]] - st1[:, engine.C["RIPTRM_STAT_RHS"]]).sum())
     else:
@@ -487,18 +530,25 @@ def main():
         dist.all_reduce(counts, op=dist.ReduceOp.SUM)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         # final gather of per-instance results (x, y, stats) over RCCL, in global instance order
-        res = eng.result()
         total = B * world
         gx = gather_rows(res.x.contiguous(), total, world, rank)
         gy = gather_rows(res.y.contiguous(), total, world, rank)
         gs = gather_rows(torch.as_tensor(res.stats, device=dev), total, world, rank)
     elif args.dump:
-        res = eng.result()
         gx, gy, gs = res.x, res.y, torch.as_tensor(res.stats)
     if args.dump and rank == 0:
         # gathered per-instance results in global instance order (tests compare them bitwise)
         np.savez(args.dump, x=gx.cpu().numpy()[:, :n], y=gy.cpu().numpy()[:, :n], stats=gs.cpu().numpy(),
                  ids=np.arange(B * world), seed0=args.seed0, outer_target=W + K)
+    if args.dump_outputs:
+        # x, y of every global instance as the timed window's last outer iteration left them
+        ox, oy = res_timed.x.contiguous(), res_timed.y.contiguous()
+        if res_timed is res and dist.is_initialized():
+            ox, oy = gx, gy      # no second window ran: the final gather above is this state
+        elif dist.is_initialized():
+            ox, oy = (gather_rows(t, B * world, world, rank) for t in (ox, oy))
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {"x": ox.cpu().numpy()[:, :n], "y": oy.cpu().numpy()[:, :n]})
     T = float(tmax.item())
     outer_all, passes_all, inner_all, tcg_all, gemv_ms_all, gemv_n_all = [float(v) for v in counts.tolist()]
 
@@ -511,7 +561,7 @@ def main():
         gemv_s = prof["gemv_ms"] / 1e3
         passes_r0 = float((st1[:, C["RIPTRM_STAT_PASSES"]] - st0[:, C["RIPTRM_STAT_PASSES"]]).sum())
         rhs_r0 = float((st1[:, C["RIPTRM_STAT_RHS"]] - st0[:, C["RIPTRM_STAT_RHS"]]).sum())
-        if graph_mode:   # kernel timing came from the profiled second window
+        if graph_mode and args.full:   # kernel timing came from the profiled second window
             passes_r0, rhs_r0 = passes_prof, rhs_prof
         achieved = (passes_r0 * bytes_per_pass / gemv_s / 1e9) if gemv_s > 0 else None
         nl = max(1, int(prof["gemv_launches"]))
@@ -530,7 +580,9 @@ def main():
             except Exception as e:  # pragma: no cover
                 log(f"traffic json unreadable: {e}")
         persist = eng.persistent_state()["active"] if args.layout == "sym" else False
-        if persist:
+        if not timed:
+            roofline = None   # no kernel was timed: the replayed graphs take a profiled window of their own (--full)
+        elif persist:
             # k_persist: the whole lock-step loop in one launch per chunk, S held in LDS.  Its time
             # is per-pass latency (barrier + reductions), not bandwidth: price the passes it served
             # at the bytes the lock-step S-pass would stream, and give the per-pass latency.
@@ -597,14 +649,16 @@ def main():
                                         "runs beside the other stream group's S-pass)"}
         spass_roofline = None
         tri_lo, tri_hi = engine.C["RIPTRM_TRS_TRI_MIN"], engine.C["RIPTRM_TRS_TRI_MAX"]
-        if args.trs == "Exact_RepMat" and 96 < n - 1 < tri_lo and rank == 0:
+        if not args.full:
+            pass              # the live-timed eigensolver / tridiagonalisation roofs are --full's
+        elif args.trs == "Exact_RepMat" and 96 < n - 1 < tri_lo and rank == 0:
             # the eigensolver, not the S-pass, sets this line's time: price it, keep the S-pass in detail
             spass_roofline, roofline = roofline, eig_roofline(n - 1, B, dev)
         elif args.trs == "Exact_RepMat" and tri_lo <= n - 1 <= tri_hi and rank == 0:
             # the tridiagonal path's subproblem service (riptrm_tri.h) sets this line's time
             spass_roofline, roofline = roofline, tri_roofline(n - 1, dev, min(B, 64))
         cpu = None
-        if args.cpu_budget > 0 and world == 1:
+        if args.full and args.cpu_budget > 0 and world == 1:
             positions = window_positions(W, K, args.cycle)
             log(f"CPU baseline (oracle) over positions {_pos_text(positions)} ...")
             ipo = (inner_all / outer_all) if outer_all > 0 else None
@@ -654,11 +708,13 @@ def main():
             "detail": {"inner_iterations_per_s": inner_all / T, "tcg_iterations_per_s": tcg_all / T,
                        "s_passes_per_s": passes_all / T,
                        "gemv_time_frac": None if graph_mode else (prof["gemv_ms"] / 1e3) / T,
-                       "kernel_timing": ("second profiled window, outer iterations "
-                                         f"{W + K + 1}..{W + 2 * K} (the timed window replays hipGraphs)")
-                       if graph_mode else "HIP events inside the timed window",
-                       "state_kernel_ms": prof["state_ms"], "state_launches": prof["state_launches"],
-                       "gemv_launches": prof["gemv_launches"],
+                       "kernel_timing": "HIP events inside the timed window" if not graph_mode else
+                                        ("second profiled window, outer iterations "
+                                         f"{W + K + 1}..{W + 2 * K} (the timed window replays hipGraphs)") if args.full else
+                                        "none (the timed window replays hipGraphs; --full profiles a second window)",
+                       "state_kernel_ms": prof["state_ms"] if timed else None,
+                       "state_launches": prof["state_launches"] if timed else None,
+                       "gemv_launches": prof["gemv_launches"] if timed else None,
                        "state_kernel_roofline": state_roofline,
                        **({"spass_roofline": spass_roofline} if spass_roofline else {}),
                        **({"spass_calibration": cal} if cal.get("ms_per_launch_tile") else {}),
@@ -677,6 +733,27 @@ def main():
         dist.destroy_process_group()
 
 
+def stiefel_cpu_baseline(n, p, B, X, W, U):
+    """CPU baseline of the Stiefel line: the pymanopt restatement (oracle/stiefel_oracle.py, NumPy) on
+    the host, over the same points until ~2 s have passed per operation (a bounded sample; BLAS
+    threads as configured).  Returns (cpu_baseline entry for the projection, retractions/s)."""
+    from oracle.stiefel_oracle import Stiefel as _CpuStiefel
+    M = _CpuStiefel(n, p)
+    Xh, Wh, Uh = X.cpu().numpy(), W.cpu().numpy(), U.cpu().numpy()
+    rates = {}
+    for name, fn in (("projection", lambda b: M.projection(Xh[b], Wh[b])),
+                     ("retraction", lambda b: M.retraction(Xh[b], Uh[b]))):
+        cnt, t0 = 0, time.perf_counter()
+        while time.perf_counter() - t0 < 2.0:
+            fn(cnt % B)
+            cnt += 1
+        rates[name] = cnt / (time.perf_counter() - t0)
+    cpu = {"value": rates["projection"], "unit": "projections/s", "cores": int(os.environ.get("OMP_NUM_THREADS", "1")),
+           "kind": "port", "sample": f"oracle/stiefel_oracle.py (NumPy) projection of the first points of the batch, "
+                                     f"{n}x{p}, repeated for 2 s on the host"}
+    return cpu, rates["retraction"]
+
+
 def bench_stiefel(args, world, rank, dev, dist):
     """Stiefel(n, p) kernels (BASELINE configs[4] size (200, 50) x 256 per GPU):
     --steps projections and retractions of the whole batch, HIP-event timed on the stream."""
@@ -690,7 +767,7 @@ def bench_stiefel(args, world, rank, dev, dist):
     W = torch.randn(B, n, p, dtype=torch.float64, device=dev, generator=g)
     st = StiefelBatch(n, p)
     U = (0.1 * st.projection(X, W)).contiguous()
-    res = {}
+    res, last = {}, {}
     for name, fn in (("projection", lambda: st.projection(X, W)), ("retraction", lambda: st.retraction(X, U))):
         for _ in range(max(1, args.warmup)):
             fn()
@@ -699,8 +776,9 @@ def bench_stiefel(args, world, rank, dev, dist):
         torch.cuda.synchronize(dev)
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record()
-        for _ in range(args.steps):
+        for _ in range(args.steps - 1):
             fn()
+        last[name] = fn()   # the last timed step's result (--dump-outputs)
         e1.record()
         torch.cuda.synchronize(dev)
         res[name] = e0.elapsed_time(e1) / 1e3 / args.steps
@@ -710,6 +788,8 @@ def bench_stiefel(args, world, rank, dev, dist):
     tp, tr = [float(v) for v in t.tolist()]
     if rank != 0:
         return
+    if args.dump_outputs:   # rank 0's batch
+        dump_outputs(args.dump_outputs, {k: v.cpu().numpy() for k, v in last.items()})
     gbs = 3.0 * n * p * 8 * B / tp / 1e9    # read X, U; write the result
     tfs = 4.0 * n * p * p * B / tp / 1e12
     hbm_floor = 3.0 * n * p * 8 * B / (HBM_PEAK_GBS * 1e9)
@@ -737,23 +817,7 @@ def bench_stiefel(args, world, rank, dev, dist):
             for kname, m in pm["kernels"].items():
                 if "read_bytes_corrected" in m and "write_bytes" in m:
                     traffic[kname.split("::")[-1].split("<")[0]] = (m["read_bytes_corrected"] + m["write_bytes"]) / pm["B"] * B
-    # CPU baseline: the pymanopt restatement (oracle/stiefel_oracle.py, NumPy) on the host, over the
-    # same points until ~2 s have passed (a bounded sample; BLAS threads as configured)
-    from oracle.stiefel_oracle import Stiefel as _CpuStiefel
-    M = _CpuStiefel(n, p)
-    Xh, Wh, Uh = X.cpu().numpy(), W.cpu().numpy(), U.cpu().numpy()
-    rates = {}
-    for name, fn in (("projection", lambda b: M.projection(Xh[b], Wh[b])),
-                     ("retraction", lambda b: M.retraction(Xh[b], Uh[b]))):
-        cnt, t0 = 0, time.perf_counter()
-        while time.perf_counter() - t0 < 2.0:
-            fn(cnt % B)
-            cnt += 1
-        rates[name] = cnt / (time.perf_counter() - t0)
-    cpu = {"value": rates["projection"], "unit": "projections/s", "cores": int(os.environ.get("OMP_NUM_THREADS", "1")),
-           "kind": "port", "sample": f"oracle/stiefel_oracle.py (NumPy) projection of the first points of the batch, "
-                                     f"{n}x{p}, repeated for 2 s on the host"}
-    cpu_retr = rates["retraction"]
+    cpu, cpu_retr = (stiefel_cpu_baseline(n, p, B, X, W, U) if args.full else (None, None))
     print(json.dumps({
         "metric": f"Stiefel({n},{p}) projections/sec, batch {B}/GPU",
         "value": B * world / tp, "unit": "projections/s", "n_gpus": world, "steps": args.steps,
@@ -1050,12 +1114,17 @@ def bench_si(args, world, rank, dev, dist):
         dist.barrier()
     kern_s = e0.elapsed_time(e1) / 1e3
     st = eng.stats()
-    # section breakdown from a second, instrumented launch (device clock per section)
-    eng.profile_enable(True)
-    eng.begin(xs, ys, opt)
-    sec = eng.profile_read()
-    eng.profile_enable(False)
-    secfrac = {k: (v / sec["total"] if sec["total"] > 0 else None) for k, v in sec.items() if k != "total"}
+    if args.dump_outputs and rank == 0:   # rank 0's batch, as the timed launch left it
+        r = eng.result()
+        dump_outputs(args.dump_outputs, {"x": r.x.cpu().numpy(), "y": r.y.cpu().numpy()})
+    sec = secfrac = None
+    if args.full:
+        # section breakdown from a second, instrumented launch (device clock per section)
+        eng.profile_enable(True)
+        eng.begin(xs, ys, opt)
+        sec = eng.profile_read()
+        eng.profile_enable(False)
+        secfrac = {k: (v / sec["total"] if sec["total"] > 0 else None) for k, v in sec.items() if k != "total"}
     C = si.C
     tot = lambda f: float(st[:, C[f"RIPTRM_STAT_{f}"]].sum())
     counts = torch.tensor([tot("OUTER_ITERS"), tot("INNER_ITERS"), tot("TCG_ITERS"), tot("PASSES")],
@@ -1070,7 +1139,7 @@ def bench_si(args, world, rank, dev, dist):
         return
     tdim = d * (d - 1) // 2 + d * (d + 1)   # manifold.dim of Product(Skew(d), SPD(d), SPD(d))
     cpu = None
-    if args.cpu_budget > 0 and world == 1:
+    if args.full and args.cpu_budget > 0 and world == 1:
         ipo = inner / outer if outer > 0 else None
         one = _si_oracle_window(0, K, args.cpu_budget, args.trs, d)
         if one is None:   # not one outer iteration within the budget: sampled per inner step
@@ -1104,12 +1173,14 @@ def bench_si(args, world, rank, dev, dist):
                                + ("" if args.trs == "tCG" else ", TRS_solver=Exact_RepMat + second-order test"),
                    "trs_solver": args.trs,
                    "global_batch": B * world, "parallelism": f"instance-sharded x{world}", "world_size": world},
-        "roofline": si_roofline(args, d, hvps, kern_s, sec, tot("PASSES")),
+        "roofline": si_roofline(args, d, hvps, kern_s, sec, tot("PASSES")) if args.full else None,
         # the HBM TRS service's eigensolver at this manifold.dim (the line's other half: DESIGN 7b)
-        **({"service_eig_roofline": eig_roofline(tdim, B, dev)} if args.trs != "tCG" and 96 < tdim < si.C["RIPTRM_TRS_TRI_MIN"] else {}),
+        **({"service_eig_roofline": eig_roofline(tdim, B, dev)}
+           if args.full and args.trs != "tCG" and 96 < tdim < si.C["RIPTRM_TRS_TRI_MIN"] else {}),
         "cpu_baseline": cpu,
         "detail": {"inner_iterations_per_s": inner / T, "tcg_iterations_per_s": tcg / T, "hvps_per_s": hvps / T,
-                   "section_fraction": secfrac, "us_per_hvp_per_instance": sec["hvp"] / max(1.0, tot("PASSES")) * 1e6,
+                   "section_fraction": secfrac,
+                   "us_per_hvp_per_instance": (sec["hvp"] / max(1.0, tot("PASSES")) * 1e6) if sec else None,
                    # HBM TRS service (Exact_RepMat, d >= 8): subproblems whose CG was decided on their
                    # eigenpairs, and CGs skipped by the certified bound (since the context was made)
                    "trs_cg_checked_skipped": (list(eng.trs_skip_stats()) if args.trs != "tCG" else None),

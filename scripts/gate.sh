@@ -56,7 +56,7 @@ step() {
       || { tail -40 $O/gpu_tests.log; return 1; }
     tail -1 $O/gpu_tests.log ;;
   headline)
-    timeout -k 10 420 python bench.py ${BENCH_ARGS:-} > $O/bench_headline.json 2> $O/bench_headline.err || { tail $O/bench_headline.err; return 1; }
+    timeout -k 10 420 python bench.py --full ${BENCH_ARGS:-} > $O/bench_headline.json 2> $O/bench_headline.err || { tail $O/bench_headline.err; return 1; }
     val $O/bench_headline.json headline ;;
   headline_prof)
     timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/head -o head -- python bench.py --cpu-budget 0 \
@@ -74,15 +74,15 @@ step() {
       --source "rocprofv3 --pmc FETCH_SIZE / --pmc WRITE_SIZE, separate passes, of python bench.py --cpu-budget 0 --warmup 1 --steps 2 ($O)" \
       && cp $O/r4_traffic_spass_sup.json profiles/ ;;   # the later headline step in this call reads it (bench.py --traffic-json)
   cfg1)
-    timeout -k 10 400 python bench.py --dim 1000 --batch 1 ${XB:-} > $O/bench_cfg1.json 2> $O/bench_cfg1.err || { tail $O/bench_cfg1.err; return 1; }
+    timeout -k 10 400 python bench.py --full --dim 1000 --batch 1 ${XB:-} > $O/bench_cfg1.json 2> $O/bench_cfg1.err || { tail $O/bench_cfg1.err; return 1; }
     val $O/bench_cfg1.json cfg1 ;;
   cfg1_trace)
     timeout -k 10 120 python scripts/persist_trace.py 1000 > $O/cfg1_trace.txt 2>&1 || { tail $O/cfg1_trace.txt; return 1; }
     tail -5 $O/cfg1_trace.txt ;;
   shared)
-    timeout -k 10 300 python bench.py --layout shared ${XB:-} > $O/bench_shared.json 2> $O/bench_shared.err || { tail $O/bench_shared.err; return 1; }
+    timeout -k 10 300 python bench.py --full --layout shared ${XB:-} > $O/bench_shared.json 2> $O/bench_shared.err || { tail $O/bench_shared.err; return 1; }
     val $O/bench_shared.json shared
-    timeout -k 10 300 python bench.py --layout shared --batch 256 ${XB:-} > $O/bench_shared_b256.json 2> $O/bench_shared_b256.err \
+    timeout -k 10 300 python bench.py --full --layout shared --batch 256 ${XB:-} > $O/bench_shared_b256.json 2> $O/bench_shared_b256.err \
       || { tail $O/bench_shared_b256.err; return 1; }
     val $O/bench_shared_b256.json shared256 ;;
   shared_prof)
@@ -90,11 +90,11 @@ step() {
       --batch 256 --cpu-budget 0 > $O/bench_shared_rocprof.json 2> $O/shared_rocprof.log || return 1
     note "shared rocprof ok" ;;
   si)
-    timeout -k 10 400 python bench.py --problem si --batch 256 ${XB:-} > $O/bench_si_b256.json 2> $O/bench_si.err || { tail $O/bench_si.err; return 1; }
+    timeout -k 10 400 python bench.py --full --problem si --batch 256 ${XB:-} > $O/bench_si_b256.json 2> $O/bench_si.err || { tail $O/bench_si.err; return 1; }
     val $O/bench_si_b256.json si ;;
   stiefel)
-    timeout -k 10 180 python bench.py --problem stiefel --dim 200 --batch 256 > $O/bench_stiefel_b256.json 2> $O/st256.err || return 1
-    timeout -k 10 180 python bench.py --problem stiefel --dim 200 --batch 2048 > $O/bench_stiefel_b2048.json 2> $O/st2048.err || return 1
+    timeout -k 10 180 python bench.py --full --problem stiefel --dim 200 --batch 256 > $O/bench_stiefel_b256.json 2> $O/st256.err || return 1
+    timeout -k 10 180 python bench.py --full --problem stiefel --dim 200 --batch 2048 > $O/bench_stiefel_b2048.json 2> $O/st2048.err || return 1
     python -c "
 import json
 for b in (256, 2048):
@@ -121,11 +121,11 @@ for b in (256, 2048):
     timeout -k 10 60 /tmp/stamps 200 50 ${ST_B:-256} > $O/stiefel_stamps.txt 2>&1 || return 1
     tail -20 $O/stiefel_stamps.txt ;;
   exact)
-    timeout -k 10 420 python bench.py --trs Exact_RepMat --dim 200 --batch 64 --steps 4 --warmup 1 --cpu-budget 60 \
+    timeout -k 10 420 python bench.py --full --trs Exact_RepMat --dim 200 --batch 64 --steps 4 --warmup 1 --cpu-budget 60 \
       > $O/bench_exact_200.json 2> $O/bench_exact.err || { tail $O/bench_exact.err; return 1; }
     val $O/bench_exact_200.json exact200 ;;
   exact1000)
-    timeout -k 10 900 python bench.py --trs Exact_RepMat --dim 1000 --batch ${EX_B:-1} --steps 3 --warmup 1 --cpu-budget 120 \
+    timeout -k 10 900 python bench.py --full --trs Exact_RepMat --dim 1000 --batch ${EX_B:-1} --steps 3 --warmup 1 --cpu-budget 120 \
       --cpu-pool-budget 150 > $O/bench_exact_1000.json 2> $O/bench_exact1000.err || { tail $O/bench_exact1000.err; return 1; }
     val $O/bench_exact_1000.json exact1000 ;;
   si_pmc)
@@ -147,7 +147,7 @@ for b in (256, 2048):
       --source "rocprofv3 --pmc SQ_WAVE_CYCLES SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU -- python bench.py --problem si --si-dim 8 --trs Exact_RepMat --batch 64 --cpu-budget 0 --steps 4 ($O)" \
       && cp $O/r5_si_pmc_d8.json profiles/ ;;
   si_d8_exact)
-    timeout -k 10 900 python bench.py --problem si --si-dim 8 --trs Exact_RepMat --batch 64 --cpu-budget 100 --cpu-pool-budget 150 \
+    timeout -k 10 900 python bench.py --full --problem si --si-dim 8 --trs Exact_RepMat --batch 64 --cpu-budget 100 --cpu-pool-budget 150 \
       --si-pmc-json profiles/r5_si_pmc_d8.json \
       > $O/bench_si_d8_exact.json 2> $O/bench_si_d8_exact.err || { tail $O/bench_si_d8_exact.err; return 1; }
     val $O/bench_si_d8_exact.json si_d8_exact ;;

@@ -74,3 +74,37 @@ def test_host_cpu_info():
     info = bench.host_cpu_info()
     assert info["os_cpu_count"] == os.cpu_count()
     assert info["cpu_model"]
+
+
+def _dir_bytes(d):
+    return sum(os.path.getsize(os.path.join(d, f)) for f in os.listdir(d))
+
+
+def test_dump_outputs_caps_the_total_and_samples_the_same_elements(tmp_path, monkeypatch):
+    """--dump-outputs: float64 .npy files; an array over its share of the byte limit is cut to the
+    same sorted sample of its elements in every call, a smaller one is written whole; the files,
+    headers included, stay within the limit."""
+    import numpy as np
+    limit = 2 * (1024 + 8 * 100)                                   # 100 doubles per array after the header allowance
+    monkeypatch.setattr(bench, "DUMP_MAX_BYTES", limit)
+    big = np.arange(7 * 90, dtype=np.float32).reshape(7, 90)
+    small = np.arange(12.0).reshape(3, 4)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), {"big": big, "small": small})
+    a, b = np.load(tmp_path / "a" / "big.npy"), np.load(tmp_path / "b" / "big.npy")
+    assert a.dtype == np.float64 and a.shape == (100,)
+    np.testing.assert_array_equal(a, b)
+    assert (np.diff(a) > 0).all() and set(a) <= set(big.reshape(-1).tolist())   # distinct elements, in order
+    s = np.load(tmp_path / "a" / "small.npy")
+    assert s.dtype == np.float64
+    np.testing.assert_array_equal(s, small)
+    assert _dir_bytes(tmp_path / "a") <= limit
+
+
+def test_dump_outputs_files_stay_within_64_mb(tmp_path):
+    """Two arrays of 40 MB each (both over their share): the files on disk total at most 64 MB."""
+    import numpy as np
+    a = np.zeros((5, 1000, 1000))
+    bench.dump_outputs(str(tmp_path), {"projection": a, "retraction": a})
+    assert _dir_bytes(tmp_path) <= 64 * 10 ** 6
+    assert np.load(tmp_path / "projection.npy").size > 3_900_000   # and the share is used, not a token sample
