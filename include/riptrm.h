@@ -491,6 +491,60 @@ int riptrm_stiefel_retr(riptrm_ctx* ctx, int32_t n, int32_t p, int32_t batch, in
 int riptrm_stiefel_ehess2rhess(riptrm_ctx* ctx, int32_t n, int32_t p, int32_t batch, int64_t stride,
                                const double* X, const double* G, const double* H, const double* U, double* out);
 
+/* ==== Rosenbrock on Grassmann(n, k) (src/Rosenbrock/coordinator.py:33-95) ========================
+ * Points X are n x k row-major with X^T X = I; v = X.flatten().  f = sum_{i < nk-1} alpha (v_{i+1} -
+ * v_i)^2 + (1 - v_i)^2 (:45-51), nk inequality constraints g_i = -v_i - lb <= 0 (:55-71).  Manifold
+ * formulas are pymanopt's Grassmann: projection U - X (X^T U), polar retraction, principal-angle
+ * distance, ehess -> rhess = P_X(H) - U (X^T G).  One workgroup of 64 ceil(nk / 64) threads runs one
+ * instance's whole RIPTRM solve (TRS_solver tCG) in one launch, every vector of the solve in LDS.
+ * alpha and lb are per instance: instance b reads alpha[b * alpha_stride], lb[b * lb_stride]
+ * (stride 0 = one value for the batch). */
+#define RIPTRM_GR_KMAX 8
+#define RIPTRM_GR_NKMAX 512
+/* src/Rosenbrock/simulator.py:107-114: 0 if numpy.linalg.matrix_rank(X) == k, else inf */
+#define RIPTRM_MANVIO_GRASSMANN_RANK 3
+
+typedef struct riptrm_gr_problem {
+    int32_t struct_size;     /* = sizeof(riptrm_gr_problem) */
+    int32_t n;               /* k <= n, n k <= RIPTRM_GR_NKMAX */
+    int32_t k;               /* 1 <= k <= RIPTRM_GR_KMAX */
+    const double* alpha;     /* device */
+    int64_t alpha_stride;
+    const double* lb;        /* device */
+    int64_t lb_stride;
+} riptrm_gr_problem;
+
+/* Workspace for a batch; -1 for sizes outside the limits above. */
+int64_t riptrm_gr_workspace_bytes(int32_t n, int32_t k, int32_t batch, int32_t log_capacity);
+/* kind: 0 = x (batch x n k), 1 = y (batch x n k), 2 = eta, 3 = Heta (batch x n k),
+ * 4 = stats (batch x RIPTRM_STAT_NFIELDS), 5 = log (batch x capacity x RIPTRM_LOG_NFIELDS). */
+int64_t riptrm_gr_workspace_offset(int32_t n, int32_t k, int32_t batch, int32_t log_capacity, int32_t kind);
+int riptrm_gr_bind(riptrm_ctx* ctx, const riptrm_gr_problem* problem, int32_t batch, void* workspace,
+                   int64_t workspace_bytes, int32_t log_capacity);
+/* out_b = HwCur_b(v_b) (RIPTRM.py:729) at (x_b, y_b, mu_b).  x, y, v, out: batch x n k; mu: batch.
+ * Asynchronous. */
+int riptrm_gr_hvp(riptrm_ctx* ctx, const double* x, const double* y, const double* mu, const double* v,
+                  double* out);
+/* tCG (RIPTRM.py:41-216) at (x_b, y_b, mu_b, Delta_b): eta / Heta into the workspace (kinds 2/3), stats
+ * TCG_LAST_J / TCG_LAST_STOP.  tCG options from opt (NULL = RIPTRM defaults).  Asynchronous. */
+int riptrm_gr_tcg(riptrm_ctx* ctx, const riptrm_options* opt, const double* x, const double* y,
+                  const double* mu, const double* delta);
+/* The manifold pieces on their own, for (x_b, u_b, y_b), each batch x n k: proj_b = P_x(u), retr_b =
+ * the polar retraction of u at x, dist_b = dist(x, y) (batch doubles), fullrank_b = 1 if
+ * numpy.linalg.matrix_rank(x) == k else 0 (batch int32).  Asynchronous. */
+int riptrm_gr_ops(riptrm_ctx* ctx, const double* x, const double* u, const double* y, double* proj,
+                  double* retr, double* dist, int32_t* fullrank);
+/* Whole RIPTRM solves (RIPTRM.py:909-976, TRS_solver tCG only) from x0, y0 (batch x n k); tables as in
+ * riptrm_solve_begin.  One launch, asynchronous: synchronise the stream, then read the workspace.  An
+ * instance whose log-barrier value, ared / pred, tCG residual or step norm is not finite stops with
+ * RIPTRM_ERR_NONFINITE at the start of its outer step; the others go on. */
+int riptrm_gr_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0, const double* y0,
+                    const double* mu_table, const double* tolL_table, const double* tolC_table,
+                    int32_t table_len);
+/* The bound shape's launch: dynamic LDS bytes and threads of a workgroup, and how many workgroups
+ * the occupancy calculator fits on one compute unit. */
+int riptrm_gr_launch_info(riptrm_ctx* ctx, int32_t* lds_bytes, int32_t* threads, int32_t* wg_per_cu);
+
 #ifdef __cplusplus
 }
 #endif

@@ -12,17 +12,20 @@ eqLagmult)`` whose ``log`` has the reference's columns, one row per inner iterat
   hand-written batched eigensolver (csrc/riptrm_eig.h) up to order 149, the hand-written
   distributed tridiagonalisation with the subproblem solved in T's coordinates (csrc/riptrm_tri.h)
   for orders 150..1024, and rocSOLVER's dsyevd only for that path's hard cases and above 1024;
-* the problem is a structured descriptor (``problems.NonnegPCAProblem`` or
-  ``si.SIProblem`` for StableIdentification) instead of a list of autograd closures, because
-  closures cannot execute on the GPU;
+* the problem is a structured descriptor (``problems.NonnegPCAProblem``, ``si.SIProblem`` for
+  StableIdentification or ``rosenbrock.RosenbrockProblem`` for Rosenbrock on Grassmann(n, k)) instead
+  of a list of autograd closures, because closures cannot execute on the GPU;
+* Rosenbrock runs with ``TRS_solver='tCG'`` (what its config selects); ``'Exact_RepMat'`` raises for
+  it: the reference's tangent basis there is a draw of ``random_tangent_vector``;
 * ``manviofun`` must be 0 or the problem's simulator function (NonnegPCA ``||x|| - 1``,
-  StableIdentification's symmetry / definiteness violation); ``callbackfun`` and wandb are not
-  supported;
-* ``do_euclidean_lincomb`` (RIPTRM.py:480-482, :514-517, :543-545) is accepted for both problems:
+  StableIdentification's symmetry / definiteness violation, Rosenbrock's rank test);
+  ``callbackfun`` and wandb are not supported;
+* ``do_euclidean_lincomb`` (RIPTRM.py:480-482, :514-517, :543-545) is accepted for every problem:
   the device evaluates the Lagrangian's derivatives in closed form, which is what both branches
   compute (the conversions are linear), up to rounding.  ``is_euclidean_embedded``
   (:567-568) is accepted for NonnegPCA (on the Sphere <egrad g_i, dx> = <rgrad g_i, dx> for
-  tangent dx) and raises for StableIdentification (a different operator on the SPD factors).
+  tangent dx) and for Rosenbrock (Euclidean metric, every dx the solver forms is horizontal) and
+  raises for StableIdentification (a different operator on the SPD factors).
 
 ``run_batch(problems)`` solves many instances of the same size at once (the reference runs its
 Hydra multi-run axis one after another, ``config_simulation.yaml:35-42``).
@@ -38,6 +41,7 @@ import torch
 
 from engine import NonnegPCABatch, REFERENCE_DEFAULTS, manvio_kind, resolve_options
 from problems import NonnegPCAProblem
+from rosenbrock import RosenbrockBatch, RosenbrockProblem, rosenbrock_manvio_kind
 from si import SIBatch, SIProblem, si_manvio_kind
 from solver_base import Output, Solver
 
@@ -46,7 +50,10 @@ def _any_manvio_kind(f):
     try:
         return manvio_kind(f)
     except Exception:
-        return si_manvio_kind(f)
+        try:
+            return si_manvio_kind(f)
+        except Exception:
+            return rosenbrock_manvio_kind(f)
 
 
 class RIPTRM(Solver):
@@ -72,7 +79,7 @@ class RIPTRM(Solver):
     def run_batch(self, problems: Sequence[Any], log_capacity: int | None = None) -> List[Output]:
         """NonnegPCA: the device log is drained to the host whenever it is half full, so logs of
         any length are complete (log_capacity = rows of the device ring, default 8192).
-        StableIdentification runs each solve in one launch: its log keeps the first
+        StableIdentification and Rosenbrock run each solve in one launch: the log keeps the first
         log_capacity/2 and the latest records.  Its capacity is the requested one (default 65536
         rows per instance), capped so the batch's log stays within SI_LOG_BYTES (256 B per row)."""
         problems = list(problems)
@@ -82,6 +89,10 @@ class RIPTRM(Solver):
             req = 65536 if log_capacity is None else int(log_capacity)
             cap = max(16, min(req, int(self.SI_LOG_BYTES // (256 * len(problems)))))
             return self._run_batch_si(problems, cap)
+        if all(isinstance(p, RosenbrockProblem) for p in problems):
+            req = 65536 if log_capacity is None else int(log_capacity)
+            cap = max(16, min(req, int(self.SI_LOG_BYTES // (256 * len(problems)))))
+            return self._run_batch_rosenbrock(problems, cap)
         if log_capacity is None:
             log_capacity = 8192
         for p in problems:
@@ -150,6 +161,29 @@ class RIPTRM(Solver):
         ys = res.y.cpu().numpy()
         return self._outputs(res, [[xs[b, 0].copy(), xs[b, 1].copy(), xs[b, 2].copy()] for b in range(B)], ys,
                              log_capacity)
+
+    def _run_batch_rosenbrock(self, problems: List[RosenbrockProblem], log_capacity: int) -> List[Output]:
+        """Rosenbrock on Grassmann(n, k) (src/Rosenbrock/coordinator.py): one workgroup per problem,
+        every solve of the batch in one launch; alpha, the bound and the start are per problem."""
+        p0 = problems[0]
+        n, k = p0.n, p0.k
+        if any((p.n, p.k) != (n, k) for p in problems):
+            raise ValueError("run_batch needs Rosenbrock problems of equal (n, k)")
+        if self.option['TRS_solver'] != 'tCG':
+            raise NotImplementedError("TRS_solver='Exact_RepMat' is not implemented for the Rosenbrock problem on "
+                                      "Grassmann(n, k): the reference's tangent basis there is a draw of "
+                                      "random_tangent_vector, so parity is unpinned; use TRS_solver='tCG'")
+        B = len(problems)
+        eng = RosenbrockBatch(n, k, B, log_capacity=log_capacity)
+        eng.load(np.array([p.alpha for p in problems]), np.array([p.lb for p in problems]))
+        self.last_layout = "rosenbrock"
+        x0 = np.stack([np.asarray(p.initialpoint, dtype=np.float64) for p in problems])
+        y0 = np.stack([np.asarray(p.initialineqLagmult, dtype=np.float64) for p in problems])
+        res = eng.solve(x0, y0, self.option)
+        self.last_batch = res
+        xs = res.x.cpu().numpy()
+        ys = res.y.cpu().numpy()
+        return self._outputs(res, [xs[b].copy() for b in range(B)], ys, log_capacity)
 
     def _outputs(self, res, xs, ys, log_capacity) -> List[Output]:
         outs = []

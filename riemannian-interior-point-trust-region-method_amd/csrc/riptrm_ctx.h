@@ -8,6 +8,8 @@
 
 namespace riptrm_si { struct Bound; }
 void riptrm_si_release(riptrm_si::Bound* s);
+namespace riptrm_gr { struct Bound; }
+void riptrm_gr_release(riptrm_gr::Bound* s);
 
 using riptrm::Layout;
 using riptrm::DevParams;
@@ -65,6 +67,8 @@ struct riptrm_ctx {
   int persist_trace_cap = 0;
   // StableIdentification binding (riptrm_si.hip)
   riptrm_si::Bound* si = nullptr;
+  // Rosenbrock on Grassmann(n, k) binding (riptrm_grassmann.hip)
+  riptrm_gr::Bound* gr = nullptr;
   // Exact_RepMat above RIPTRM_TRS_DIM_MAX (riptrm_trs_big.hip): caller-owned scratch bound by
   // riptrm_trs_bind_workspace (slots of order big_order) and the rocBLAS handle of rocSOLVER
   char* big_ws = nullptr;

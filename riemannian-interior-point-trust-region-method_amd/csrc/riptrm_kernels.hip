@@ -3079,6 +3079,7 @@ int riptrm_ctx_destroy(riptrm_ctx* ctx) {
   if (ctx) {
     if (ctx->gexec) (void)hipGraphExecDestroy(ctx->gexec);
     if (ctx->si) riptrm_si_release(ctx->si);
+    if (ctx->gr) riptrm_gr_release(ctx->gr);
     riptrm_big_release(ctx);
     for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
     for (auto e : {ctx->ev_fork, ctx->ev_join, ctx->ev_pass[0], ctx->ev_pass[1]})

@@ -48,6 +48,14 @@ class RiptrmSIProblem(ctypes.Structure):
     ]
 
 
+class RiptrmGRProblem(ctypes.Structure):
+    """Mirror of ``riptrm_gr_problem`` (include/riptrm.h)."""
+    _fields_ = [
+        ("struct_size", c_int32), ("n", c_int32), ("k", c_int32),
+        ("alpha", c_void_p), ("alpha_stride", c_int64), ("lb", c_void_p), ("lb_stride", c_int64),
+    ]
+
+
 # (restype, argtypes) of every exported symbol
 SIGNATURES: Dict[str, tuple] = {
     "riptrm_abi_version": (c_int32, []),
@@ -111,6 +119,15 @@ SIGNATURES: Dict[str, tuple] = {
                                  c_double, c_void_p, c_void_p, c_void_p, c_void_p]),
     "riptrm_si_solve": (c_int32, [c_void_p, ctypes.POINTER(RiptrmOptions), c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int32]),
+    "riptrm_gr_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "riptrm_gr_workspace_offset": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "riptrm_gr_bind": (c_int32, [c_void_p, ctypes.POINTER(RiptrmGRProblem), c_int32, c_void_p, c_int64, c_int32]),
+    "riptrm_gr_hvp": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "riptrm_gr_tcg": (c_int32, [c_void_p, ctypes.POINTER(RiptrmOptions), c_void_p, c_void_p, c_void_p, c_void_p]),
+    "riptrm_gr_ops": (c_int32, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "riptrm_gr_solve": (c_int32, [c_void_p, ctypes.POINTER(RiptrmOptions), c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_int32]),
+    "riptrm_gr_launch_info": (c_int32, [c_void_p, P_int32, P_int32, P_int32]),
 }
 
 

@@ -1,0 +1,121 @@
+#!/usr/bin/env python3
+"""Throughput of the Rosenbrock-on-Grassmann solve (csrc/riptrm_grassmann.hip) next to the CPU oracle.
+
+256 instances with alpha log-spaced over [1, 1e7] at (n, k) = (5, 3) and (16, 4), the coordinator's
+start (I[:, :k], y0 = 1), maxiter 8, tolresid 0, TRS_solver tCG.  maxiter is 8 so that every instance
+runs to completion on both legs: from outer iteration 9 on (mu < 4e-4) some of these instances need 10^4
+and more inner iterations per outer iteration, on the CPU as on the GPU, and a run to maxiter 20 is
+minutes per instance.  maxtime (60 s) is a guard only: the result counts the instances it stopped, and
+the rates mean what they say only when that count is 0 on both legs.
+
+GPU: the whole batch is ONE launch (one workgroup per instance).  After one warm-up solve of the same
+shape, HIP events are recorded on the stream right before and right after the solve call with the start
+points already on the device; the call enqueues the upload of the three option tables (a few hundred
+bytes) and the launch.  Median of REPEATS timed solves.  Outer it/s = the outer iterations the batch
+completed (stats OUTER_ITERS) over that time.
+CPU: tests/rosenbrock_oracle.solve (RosenbrockVectorized) on the same instances on a 16-process pool,
+wall clock around the pool's map (the pool is started and warmed before).
+Prints one JSON line; --out FILE also writes it there.  Needs the GPU: no fallback.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "riemannian-interior-point-trust-region-method_amd")):
+    if p not in sys.path:
+        sys.path.insert(0, p)
+
+BATCH, MAXITER, REPEATS, MAXTIME = 256, 8, 3, 60.0
+SHAPES = [(5, 3), (16, 4)]
+
+
+def _cpu_job(job):
+    import rosenbrock_oracle as R
+    n, k, alpha = job
+    res = R.solve(n, k, alpha, option=dict(maxiter=MAXITER, tolresid=0.0, maxtime=MAXTIME))
+    return res.outer_iterations, res.inner_iterations, str(res.stoppingcriterion).startswith("Max time")
+
+
+def gpu_leg(n, k, alphas):
+    import torch
+    import rosenbrock
+    eng = rosenbrock.RosenbrockBatch(n, k, len(alphas), log_capacity=64).load(alphas)
+    opt = {"TRS_solver": "tCG", "second_order_stationarity": False, "manviofun": rosenbrock.manviofun,
+           "tolresid": 0.0, "maxtime": MAXTIME, "maxiter": MAXITER}
+    x0 = torch.as_tensor(np.stack([np.eye(n)[:, :k]] * len(alphas))).to(eng.device).contiguous()
+    y0 = torch.ones((len(alphas), n * k), dtype=torch.float64, device=eng.device)
+    res = eng.solve(x0, y0, opt)   # warm-up: loads the code object
+    times = []
+    for _ in range(REPEATS):
+        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize(eng.device)
+        a.record()
+        eng.begin(x0, y0, opt)
+        b.record()
+        b.synchronize()
+        times.append(a.elapsed_time(b) * 1e-3)
+        res = eng.result()
+    outer = float(res.stats[:, rosenbrock.C["RIPTRM_STAT_OUTER_ITERS"]].sum())
+    inner = float(res.stats[:, rosenbrock.C["RIPTRM_STAT_INNER_ITERS"]].sum())
+    errors = int((res.stats[:, rosenbrock.C["RIPTRM_STAT_ERROR"]] != 0).sum())
+    timed_out = int((res.stats[:, rosenbrock.C["RIPTRM_STAT_STOP_CODE"]] == rosenbrock.C["RIPTRM_STOP_MAXTIME"]).sum())
+    t = float(np.median(times))
+    return {"seconds": t, "seconds_all": times, "outer_iterations": outer, "inner_iterations": inner,
+            "outer_it_per_s": outer / t, "inner_it_per_s": inner / t, "instances_with_error": errors,
+            "instances_stopped_by_maxtime": timed_out, **eng.launch_info()}
+
+
+def cpu_leg(pool, n, k, alphas):
+    jobs = [(n, k, float(a)) for a in alphas]
+    t0 = time.perf_counter()
+    out = pool.map(_cpu_job, jobs, chunksize=1)
+    t = time.perf_counter() - t0
+    outer = float(sum(o for o, _, _ in out))
+    inner = float(sum(i for _, i, _ in out))
+    return {"seconds": t, "outer_iterations": outer, "inner_iterations": inner,
+            "outer_it_per_s": outer / t, "inner_it_per_s": inner / t,
+            "instances_stopped_by_maxtime": int(sum(m for _, _, m in out))}
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--out", default=None, help="also write the JSON line to this file")
+    ap.add_argument("--procs", type=int, default=16, help="CPU pool size")
+    args = ap.parse_args()
+    import multiprocessing as mp
+    if not os.path.exists("/dev/kfd"):
+        raise SystemExit("rosenbrock_bench needs the GPU")
+    alphas = np.logspace(0, 7, BATCH)
+    # the pool forks, and finishes, before this process touches the GPU
+    pool = mp.get_context("fork").Pool(args.procs)
+    pool.map(_cpu_job, [(5, 3, 1.0)] * args.procs, chunksize=1)   # warm the workers (imports)
+    result = {"metric": "outer RIPTRM iterations/s, Rosenbrock on Grassmann(n, k), 256 instances, one launch",
+              "batch": BATCH, "maxiter": MAXITER, "maxtime_s": MAXTIME, "alpha": "logspace(0, 7, 256)", "dtype": "f64",
+              "cpu_pool_processes": args.procs, "shapes": {}}
+    cpu = {s: cpu_leg(pool, s[0], s[1], alphas) for s in SHAPES}
+    pool.close()
+    pool.join()
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("rosenbrock_bench needs the GPU")
+    for (n, k) in SHAPES:
+        g = gpu_leg(n, k, alphas)
+        c = cpu[(n, k)]
+        result["shapes"][f"{n}x{k}"] = {"gpu": g, "cpu_pool": c,
+                                        "gpu_over_cpu_pool": g["outer_it_per_s"] / c["outer_it_per_s"],
+                                        "gpu_over_cpu_pool_inner": g["inner_it_per_s"] / c["inner_it_per_s"]}
+    line = json.dumps(result)
+    print(line)
+    if args.out:
+        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+        with open(args.out, "w") as f:
+            f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
