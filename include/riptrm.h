@@ -545,6 +545,43 @@ int riptrm_gr_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0
  * the occupancy calculator fits on one compute unit. */
 int riptrm_gr_launch_info(riptrm_ctx* ctx, int32_t* lds_bytes, int32_t* threads, int32_t* wg_per_cu);
 
+/* ---- second-order residual (src/Rosenbrock/simulator.py:60-105) -------------------------------------
+ * Per point (x, y): the eigenvalues of the Lagrangian's Hessian restricted to the horizontal directions
+ * orthogonal to the active constraints' gradients.  The device represents the SYMMETRIC PART of
+ * pymanopt's ehess -> rhess operator, H_s(V) = P_X(T V) - V sym(X^T G_L), G_L = egrad f - Y: the
+ * operator itself is not self-adjoint on this problem (X^T G_L is not symmetric), so the reference's
+ * upper-triangle matrix depends on its drawn tangent basis; H_s does not, and equals the reference's
+ * operator whenever X^T G_L is symmetric.  Output fields per point: */
+#define RIPTRM_GR_SO_MINEIG 0    /* smallest eigenvalue; 0 when nulldim == 0 (simulator.py:91-92) */
+#define RIPTRM_GR_SO_MAXEIG 1    /* largest eigenvalue; NaN when nulldim == 0 */
+#define RIPTRM_GR_SO_COND 2      /* maxeig / mineig in IEEE arithmetic (:96); NaN when nulldim == 0 (None, :93) */
+#define RIPTRM_GR_SO_NULLDIM 3   /* k (n - k) - nindep */
+#define RIPTRM_GR_SO_NACTIVE 4   /* |{i : |-v_i - lb| < active_tol}| (:15-24) */
+#define RIPTRM_GR_SO_NINDEP 5    /* active gradients kept: index order, modified Gram-Schmidt twice, residual norm
+                                  * > linindtol; a dropped gradient is not used again (the reference normalises
+                                  * its rounding residue into a direction, :26-44) */
+#define RIPTRM_GR_SO_INFO 6      /* 0, or 1: a non-finite x, y, mu or matrix entry, or an instance index outside
+                                  * the bound batch; every other field of that point is then NaN */
+#define RIPTRM_GR_SO_NFIELDS 7
+/* x, y: device, point p at x + p * point_stride (n k doubles each, point_stride >= n k).  inst: device int32,
+ * point p reads alpha and lb of bound instance inst[p]; NULL = instance p (then npoints <= the bound batch).
+ * active_tol: device, point p reads active_tol[p * active_tol_stride], stride 0 or 1.  barrier = 0: the
+ * Lagrangian's Hessian (simulator.py:74-85); barrier = 1: HwCur (RIPTRM.py:729), with the term
+ * (Y o P_X V) / S, symmetrised the same way.  mu: device, one per point or NULL, read only when
+ * barrier = 1 (HwCur itself does not contain mu; a non-finite one marks the point).  out: device,
+ * npoints x RIPTRM_GR_SO_NFIELDS doubles.  Needs 1 <= k (n - k) <= RIPTRM_TRS_DIM_MAX of the bound shape.
+ * One workgroup per point, asynchronous on the context's stream. */
+int riptrm_gr_second_order(riptrm_ctx* ctx, const double* x, const double* y, int64_t point_stride,
+                           const int32_t* inst, int32_t npoints, const double* active_tol,
+                           int64_t active_tol_stride, double linindtol, int32_t barrier, const double* mu,
+                           double* out);
+/* The trail: while one is bound, riptrm_gr_solve stores the evaluated (x, y) of every log record, 2 n k
+ * doubles (x, then y), at trail + ((b * log_capacity + slot) * 2 n k) with the record's own log slot ("Log
+ * slots": the head and a ring of the latest records), log_capacity the bound one.  NULL unbinds;
+ * riptrm_gr_bind unbinds too.  With no trail bound the solve launches the kernel it always did. */
+int64_t riptrm_gr_trail_bytes(int32_t n, int32_t k, int32_t batch, int32_t log_capacity);
+int riptrm_gr_bind_trail(riptrm_ctx* ctx, void* trail, int64_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

@@ -19,7 +19,11 @@ eqLagmult)`` whose ``log`` has the reference's columns, one row per inner iterat
   it: the reference's tangent basis there is a draw of ``random_tangent_vector``;
 * ``manviofun`` must be 0 or the problem's simulator function (NonnegPCA ``||x|| - 1``,
   StableIdentification's symmetry / definiteness violation, Rosenbrock's rank test);
-  ``callbackfun`` and wandb are not supported;
+  ``callbackfun`` must be None or return ``eval`` unchanged, except for Rosenbrock, where the simulator's
+  second-order residual (``src/Rosenbrock/simulator.py:100-105`` or ``rosenbrock.callbackfun``) runs on
+  the device after the solve, over the stored point of every log row, and adds the columns
+  ``second_order_residual`` and ``condition_number`` (the symmetric part of the Hessian, DESIGN.md 7e);
+  wandb is not supported;
 * ``do_euclidean_lincomb`` (RIPTRM.py:480-482, :514-517, :543-545) is accepted for every problem:
   the device evaluates the Lagrangian's derivatives in closed form, which is what both branches
   compute (the conversions are linear), up to rounding.  ``is_euclidean_embedded``
@@ -41,7 +45,8 @@ import torch
 
 from engine import NonnegPCABatch, REFERENCE_DEFAULTS, manvio_kind, resolve_options
 from problems import NonnegPCAProblem
-from rosenbrock import RosenbrockBatch, RosenbrockProblem, rosenbrock_manvio_kind
+from rosenbrock import (CALLBACK_NONE, RosenbrockBatch, RosenbrockProblem, rosenbrock_callback_kind,
+                        rosenbrock_manvio_kind)
 from si import SIBatch, SIProblem, si_manvio_kind
 from solver_base import Output, Solver
 
@@ -68,7 +73,11 @@ class RIPTRM(Solver):
         self.name = f"RIPTRM_{self.option['TRS_solver']}"
         self.initialize_wandb()
         # validate early (raises on unsupported options)
-        resolve_options(self.option, np.pi, 1, manvio_classifier=_any_manvio_kind)
+        ro = resolve_options(self.option, np.pi, 1, manvio_classifier=_any_manvio_kind,
+                             callback_classifier=rosenbrock_callback_kind)
+        self.callback_kind = ro.callback_kind
+        if self.callback_kind == CALLBACK_NONE:
+            self.option['callbackfun'] = None   # a callback that returns eval unchanged: nothing to run
         self.last_batch = None
 
     def run(self, problem) -> Output:
@@ -85,6 +94,9 @@ class RIPTRM(Solver):
         problems = list(problems)
         if not problems:
             return []
+        if self.callback_kind != CALLBACK_NONE and not all(isinstance(p, RosenbrockProblem) for p in problems):
+            raise NotImplementedError("callbackfun cannot run on the device (only the Rosenbrock simulator's "
+                                      "second-order residual does, on Rosenbrock problems)")
         if all(isinstance(p, SIProblem) for p in problems):
             req = 65536 if log_capacity is None else int(log_capacity)
             cap = max(16, min(req, int(self.SI_LOG_BYTES // (256 * len(problems)))))
@@ -174,9 +186,17 @@ class RIPTRM(Solver):
                                       "Grassmann(n, k): the reference's tangent basis there is a draw of "
                                       "random_tangent_vector, so parity is unpinned; use TRS_solver='tCG'")
         B = len(problems)
+        if self.callback_kind != CALLBACK_NONE:
+            from engine import C
+            if k * (n - k) > C["RIPTRM_TRS_DIM_MAX"]:
+                raise NotImplementedError(f"callbackfun: the second-order residual needs manifold dimension k (n - k) "
+                                          f"<= {C['RIPTRM_TRS_DIM_MAX']} (got {k * (n - k)} at n = {n}, k = {k})")
+            # the trail keeps 2 n k doubles per log row: log + trail stay within SI_LOG_BYTES
+            log_capacity = max(16, min(log_capacity, int(self.SI_LOG_BYTES // ((256 + 16 * n * k) * B))))
         eng = RosenbrockBatch(n, k, B, log_capacity=log_capacity)
         eng.load(np.array([p.alpha for p in problems]), np.array([p.lb for p in problems]))
         self.last_layout = "rosenbrock"
+        self.last_engine = eng   # with a callback: its trail holds the point of every log row
         x0 = np.stack([np.asarray(p.initialpoint, dtype=np.float64) for p in problems])
         y0 = np.stack([np.asarray(p.initialineqLagmult, dtype=np.float64) for p in problems])
         res = eng.solve(x0, y0, self.option)

@@ -10,6 +10,8 @@ namespace riptrm_si { struct Bound; }
 void riptrm_si_release(riptrm_si::Bound* s);
 namespace riptrm_gr { struct Bound; }
 void riptrm_gr_release(riptrm_gr::Bound* s);
+// the bound problem and batch, for the other Grassmann translation unit (riptrm_grassmann_so.hip)
+const riptrm_gr_problem* riptrm_gr_bound_problem(const riptrm_gr::Bound* s, int32_t* batch);
 
 using riptrm::Layout;
 using riptrm::DevParams;

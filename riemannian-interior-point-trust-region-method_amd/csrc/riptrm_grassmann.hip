@@ -67,6 +67,7 @@ struct GRParams {
   double* heta;    // batch x N
   double* stats;   // batch x RIPTRM_STAT_NFIELDS
   double* log;     // batch x cap x RIPTRM_LOG_NFIELDS
+  double* trail;   // batch x cap x 2 N: the (x, y) of every log record (TRAIL instantiation), or null
   const double* in_x;
   const double* in_y;
   const double* in_mu;
@@ -113,7 +114,7 @@ struct Info {  // inner-iteration record of solver_status (RIPTRM.py:986-1023)
   double has, num, status, tr, dxtype, normdx, minx, miny, compl_, hasratio, ratio, ru, dc;
 };
 
-template <int NT>
+template <int NT, bool TRAIL>
 struct Eng {
   const GRParams& P;
   const int b, l, n, k, N, kk;
@@ -448,6 +449,14 @@ struct Eng {
 
   __device__ __forceinline__ void log_row(const double (&ev)[10], double outer_it, double mu, const Info* inf,
                                           double tcg_iters, double t_now, double t_start, double& count, double& overflow) {
+    if constexpr (TRAIL) {   // the evaluated point into the record's own slot (X, Y are what evaluation() read)
+      const int64_t capt = P.opt.log_capacity < P.cap ? P.opt.log_capacity : P.cap;
+      if (capt > 0 && act) {
+        double* Tp = P.trail + ((int64_t)b * P.cap + riptrm::log_slot((int)count, capt)) * (2 * (int64_t)N);
+        Tp[l] = X[l];
+        Tp[N + l] = Y[l];
+      }
+    }
     if (l == 0) {
       const int cnt = (int)count;
       const int64_t capl = P.opt.log_capacity < P.cap ? P.opt.log_capacity : P.cap;
@@ -771,12 +780,12 @@ struct Eng {
   }
 };
 
-template <int NT>
+template <int NT, bool TRAIL>
 __global__ void __launch_bounds__(NT) k_gr(GRParams P) {
   extern __shared__ double gr_lds[];
   const int b = blockIdx.x;
   if (b >= P.batch) return;
-  Eng<NT> e(P, b, gr_lds);
+  Eng<NT, TRAIL> e(P, b, gr_lds);
   if (P.mode == MODE_SOLVE) e.solve();
   else if (P.mode == MODE_HVP) e.op_hvp();
   else if (P.mode == MODE_TCG) e.op_tcg();
@@ -788,6 +797,7 @@ struct Bound {
   int batch = 0, cap = 0;
   Layout L{};
   char* ws = nullptr;
+  double* trail = nullptr;   // riptrm_gr_bind_trail
 };
 
 }  // namespace riptrm_gr
@@ -795,6 +805,10 @@ struct Bound {
 using namespace riptrm_gr;
 
 void riptrm_gr_release(riptrm_gr::Bound* s) { delete s; }
+const riptrm_gr_problem* riptrm_gr_bound_problem(const riptrm_gr::Bound* s, int32_t* batch) {
+  *batch = s->batch;
+  return &s->prob;
+}
 
 static bool gr_dims_ok(int32_t n, int32_t k, int32_t batch, int32_t cap) {
   return k >= 1 && k <= KMAX && n >= k && (int64_t)n * k <= NKMAX && batch >= 1 && cap >= 0;
@@ -830,7 +844,8 @@ static GRParams gr_params(riptrm_ctx* c, int mode) {
 template <int NT>
 static int gr_launch_nt(riptrm_ctx* c, const GRParams& P) {
   const size_t shm = (size_t)gr_lds_doubles(NT) * sizeof(double);
-  hipLaunchKernelGGL(k_gr<NT>, dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+  if (P.trail) hipLaunchKernelGGL((k_gr<NT, true>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+  else hipLaunchKernelGGL((k_gr<NT, false>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
   HIPCHK(c, hipGetLastError());
   return RIPTRM_OK;
 }
@@ -850,7 +865,7 @@ static int gr_launch(riptrm_ctx* c, const GRParams& P) {
 
 template <int NT>
 static hipError_t gr_occupancy_nt(int* wg) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg, (const void*)k_gr<NT>, NT,
+  return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg, (const void*)k_gr<NT, false>, NT,
                                                       (size_t)gr_lds_doubles(NT) * sizeof(double));
 }
 
@@ -895,6 +910,25 @@ int riptrm_gr_bind(riptrm_ctx* ctx, const riptrm_gr_problem* prob, int32_t batch
   ctx->gr->cap = cap;
   ctx->gr->L = L;
   ctx->gr->ws = (char*)ws;
+  ctx->gr->trail = nullptr;
+  return RIPTRM_OK;
+}
+
+int64_t riptrm_gr_trail_bytes(int32_t n, int32_t k, int32_t batch, int32_t cap) {
+  if (!gr_dims_ok(n, k, batch, cap)) return -1;
+  return 8LL * batch * cap * 2 * n * k;
+}
+
+int riptrm_gr_bind_trail(riptrm_ctx* ctx, void* trail, int64_t bytes) {
+  if (!ctx) return RIPTRM_E_ARG;
+  if (!ctx->gr) return fail(ctx, RIPTRM_E_STATE, "gr_bind_trail: riptrm_gr_bind first");
+  Bound* s = ctx->gr;
+  if (trail) {
+    if (((uintptr_t)trail % 8) != 0) return fail(ctx, RIPTRM_E_ARG, "gr_bind_trail: the trail must be 8-byte aligned");
+    if (s->cap < 1 || bytes < riptrm_gr_trail_bytes(s->prob.n, s->prob.k, s->batch, s->cap))
+      return fail(ctx, RIPTRM_E_ARG, "gr_bind_trail: trail too small (riptrm_gr_trail_bytes of the bound shape)");
+  }
+  s->trail = (double*)trail;
   return RIPTRM_OK;
 }
 
@@ -966,6 +1000,7 @@ int riptrm_gr_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0
   P.tolL_tab = tolL_table;
   P.tolC_tab = tolC_table;
   P.tab_len = table_len;
+  P.trail = ctx->gr->trail;   // only the solve logs: the operator entry points launch the plain kernel
   return gr_launch(ctx, P);
 }
 

@@ -142,6 +142,7 @@ class ResolvedOptions:
     tolL_tab: List[float]
     tolC_tab: List[float]
     tol2_tab: List[float]
+    callback_kind: int = 0   # what callback_classifier made of 'callbackfun' (0: none)
 
     @property
     def exact(self) -> bool:
@@ -161,7 +162,10 @@ class ResolvedOptions:
 
 
 def resolve_options(option: Dict[str, Any], typical_dist: float, log_capacity: int,
-                    restart_every: int = 0, manvio_classifier=None) -> ResolvedOptions:
+                    restart_every: int = 0, manvio_classifier=None, callback_classifier=None) -> ResolvedOptions:
+    """callback_classifier: None (any 'callbackfun' other than None raises), or a function that maps the
+    option to a kind the caller's engine serves on the device (0: none, e.g. a callback that returns
+    eval unchanged) and raises NotImplementedError for everything else."""
     o = dict(REFERENCE_DEFAULTS)
     o.update(option or {})
     if o['TRS_solver'] not in ('tCG', 'Exact_RepMat'):
@@ -170,7 +174,10 @@ def resolve_options(option: Dict[str, Any], typical_dist: float, log_capacity: i
         raise NotImplementedError("checkTRSoptimality (a diagnostic print, RIPTRM.py:367-391) is not on the device path")
     if o.get('use_rand'):
         raise NotImplementedError("use_rand tCG start is not on the reference's path (RIPTRM.py:450)")
-    if o.get('callbackfun') is not None:
+    callback_kind = 0
+    if callback_classifier is not None:
+        callback_kind = int(callback_classifier(o.get('callbackfun')))
+    elif o.get('callbackfun') is not None:
         raise NotImplementedError("callbackfun cannot run on the device")
     if o.get('wandb_logging'):
         raise NotImplementedError("wandb logging is not available")
@@ -206,7 +213,7 @@ def resolve_options(option: Dict[str, Any], typical_dist: float, log_capacity: i
     c.trs_solver = C["RIPTRM_TRS_SOLVER_EXACT_REPMAT"] if exact else C["RIPTRM_TRS_SOLVER_TCG"]
     c.second_order_stationarity = 1 if sos else 0
     c.trs_tolhardcase = float(o['TRS_tolhardcase'])
-    return ResolvedOptions(o, c, tab, tolL, tolC, tol2)
+    return ResolvedOptions(o, c, tab, tolL, tolC, tol2, callback_kind)
 
 
 def _stream_handle(device: torch.device) -> int:
@@ -661,6 +668,7 @@ class BatchResult:
     raw_log: List[np.ndarray]        # per instance: its log records in order (NLOG doubles each)
     ro: ResolvedOptions
     dropped: Optional[np.ndarray] = None   # per instance: records lost from the middle of the log
+    callback_cols: Optional[List[Dict[str, list]]] = None   # per instance: the callback's columns, a value per row
 
     def stat(self, b: int, name: str) -> float:
         return float(self.stats[b, C[f"RIPTRM_STAT_{name}"]])
@@ -728,6 +736,18 @@ class BatchResult:
                 dc = int(r[F("DUAL_CLIPPING")])
                 cols["dual_clipping"].append(None if (not has or dc < 0) else bool(dc))
             cols["maxabsLagmult"].append(np.float64(r[F("MAXABSLAGMULT")]))
+        if self.callback_cols is not None:
+            # callback keys follow the evaluation's (utils.py:356-366), so after "meanviolation"
+            extra_cols = self.callback_cols[b]
+            if any(len(v) != len(rows) for v in extra_cols.values()):
+                raise RuntimeError("callback columns do not match the log's length")
+            merged: Dict[str, list] = {}
+            for key, val in cols.items():
+                merged[key] = val
+                if key == "meanviolation":
+                    for ck, cv in extra_cols.items():
+                        merged[ck] = list(cv)
+            cols = merged
         return cols
 
     def tcg_iters_per_row(self, b: int) -> List[int]:

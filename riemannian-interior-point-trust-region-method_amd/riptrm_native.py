@@ -128,6 +128,10 @@ SIGNATURES: Dict[str, tuple] = {
     "riptrm_gr_solve": (c_int32, [c_void_p, ctypes.POINTER(RiptrmOptions), c_void_p, c_void_p, c_void_p, c_void_p,
                                   c_void_p, c_int32]),
     "riptrm_gr_launch_info": (c_int32, [c_void_p, P_int32, P_int32, P_int32]),
+    "riptrm_gr_second_order": (c_int32, [c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_int64,
+                                         c_double, c_int32, c_void_p, c_void_p]),
+    "riptrm_gr_trail_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "riptrm_gr_bind_trail": (c_int32, [c_void_p, c_void_p, c_int64]),
 }
 
 

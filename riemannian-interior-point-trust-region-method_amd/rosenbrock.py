@@ -8,6 +8,10 @@ Hydra sweep axes: alpha, the bound, start points -- inside ONE HIP launch, one w
 instance (``csrc/riptrm_grassmann.hip``: 64 ceil(n k / 64) threads, one per entry of the point,
 1 <= k <= RIPTRM_GR_KMAX, n k <= RIPTRM_GR_NKMAX).  ``TRS_solver='tCG'`` (what
 ``src/Rosenbrock/config_simulation.yaml`` selects) only.  No CPU fallback.
+
+The simulator's ``callbackfun`` (``src/Rosenbrock/simulator.py:60-105``: the second-order residual and the
+condition number on every log row) runs on the device too, one workgroup per log row after the solve
+(``csrc/riptrm_grassmann_so.hip``, ``RosenbrockBatch.second_order``, k (n - k) <= RIPTRM_TRS_DIM_MAX).
 """
 from __future__ import annotations
 
@@ -114,6 +118,185 @@ def rosenbrock_manvio_kind(f) -> int:
                               "(src/Rosenbrock/simulator.py:107-114)")
 
 
+CALLBACK_NONE, CALLBACK_SECOND_ORDER = 0, 1
+ACTIVE_TOL, LININDTOL = 1e-5, 1e-12   # src/Rosenbrock/simulator.py:15, :60
+
+
+def callbackfun(problem, x, y, z, eval):
+    """``option["callbackfun"]`` with the reference's signature (src/Rosenbrock/simulator.py:100-105) for
+    a ``RosenbrockProblem``: adds ``second_order_residual`` and ``condition_number`` at (x, y), computed by
+    ``riptrm_gr_second_order`` (one point, one launch).  ``RIPTRM.run`` does not call it per row: it
+    recognises it (``rosenbrock_callback_kind``) and evaluates every log row's point in one launch after
+    the solve."""
+    eng = RosenbrockBatch(problem.n, problem.k, 1, log_capacity=0).load(problem.alpha, problem.lb)
+    so = eng.second_order(np.asarray(x, dtype=np.float64)[None], np.asarray(y, dtype=np.float64)[None])
+    cols = second_order_columns(so)
+    eval["second_order_residual"] = cols["second_order_residual"][0]
+    eval["condition_number"] = cols["condition_number"][0]
+    return eval
+
+
+def second_order_columns(so: Dict[str, np.ndarray]) -> Dict[str, list]:
+    """The two log columns of ``RosenbrockBatch.second_order``'s result: the device's NaN condition
+    number (nulldim == 0, or a point it marked non-finite) is the reference's ``None``."""
+    return {"second_order_residual": [np.float64(v) for v in so["mineig"]],
+            "condition_number": [None if np.isnan(v) else np.float64(v) for v in so["cond"]]}
+
+
+def symmetric_second_order(n, k, alpha, lb, x, y, active_tol=ACTIVE_TOL):
+    """(mineig, cond or None) of the symmetric-part operator H_s(V) = P_X(T V) - V sym(X^T G_L) on the
+    horizontal directions orthogonal to the active gradients, in numpy on the host.  Only the callback
+    classifier's probe uses it (Grassmann(3, 1)); solves use the device kernel."""
+    x = np.asarray(x, dtype=np.float64).reshape(n, k)
+    N = n * k
+
+    def Tu(u):
+        w = u.ravel()
+        dd = w[1:] - w[:-1]
+        acc = np.zeros(N)
+        acc[:-1] = -2.0 * alpha * dd + 2.0 * w[:-1]
+        acc[1:] += 2.0 * alpha * dd
+        return acc.reshape(n, k)
+
+    two = np.full(N, 2.0)
+    two[-1] = 0.0
+    GL = Tu(x) - two.reshape(n, k) - np.asarray(y, dtype=np.float64).reshape(n, k)
+    xg = x.T @ GL
+    sg = 0.5 * (xg + xg.T)
+    Q = np.linalg.qr(x, mode="complete")[0][:, k:]
+    frame = [np.outer(Q[:, a], np.eye(k)[b]) for a in range(n - k) for b in range(k)]
+    proj = lambda u: u - x @ (x.T @ u)
+    M = np.array([[np.sum(f * (proj(Tu(g)) - g @ sg)) for g in frame] for f in frame])
+    M = 0.5 * (M + M.T)
+    act = [i for i in range(N) if abs(-x.ravel()[i] - lb) < active_tol]
+    Z = np.eye(len(frame))
+    if act:
+        G = np.array([[-f.ravel()[i] for i in act] for f in frame])
+        U, sv, _ = np.linalg.svd(G, full_matrices=True)
+        Z = U[:, int(np.sum(sv > 1e-10)):]
+    if Z.shape[1] == 0:
+        return 0, None
+    ev = np.linalg.eigvalsh(Z.T @ M @ Z)
+    return ev[0], ev[-1] / ev[0]
+
+
+class _CallbackProbeManifold:
+    """What src/Rosenbrock/simulator.py:26-58 and utils.orthogonalize / selfadj_operator2matrix read of
+    pymanopt's Grassmann(n, k)."""
+
+    def __init__(self, n, k):
+        self._n, self._p, self._k = n, k, 1
+        self.dim = k * (n - k)
+        self._rs = np.random.RandomState(0)
+
+    def inner_product(self, x, u, v):
+        return np.tensordot(u, v, axes=u.ndim)
+
+    def norm(self, x, v):
+        return np.linalg.norm(v)
+
+    def projection(self, x, u):
+        return u - x @ (x.T @ u)
+
+    to_tangent_space = projection
+
+    def zero_vector(self, x):
+        return np.zeros_like(x)
+
+    def random_tangent_vector(self, x):
+        v = self.projection(x, self._rs.randn(*x.shape))
+        return v / np.linalg.norm(v)
+
+
+class _CallbackProbeProblem:
+    """A structured Rosenbrock problem with the attributes simulator.py:60-98 reads."""
+
+    def __init__(self, n, k, alpha, lb):
+        self.n, self.k, self.alpha, self.lb = n, k, float(alpha), float(lb)
+        M = self.manifold = _CallbackProbeManifold(n, k)
+        N = n * k
+        two = np.full(N, 2.0)
+        two[-1] = 0.0
+
+        def Tu(u):
+            w = u.ravel()
+            dd = w[1:] - w[:-1]
+            acc = np.zeros(N)
+            acc[:-1] = -2.0 * alpha * dd + 2.0 * w[:-1]
+            acc[1:] += 2.0 * alpha * dd
+            return acc.reshape(n, k)
+
+        egrad = lambda x: Tu(x) - two.reshape(n, k)
+        self.riemannian_hessian = lambda x, v: M.projection(x, Tu(v)) - v @ (x.T @ egrad(x))
+        unit = lambda i: -np.eye(N)[i].reshape(n, k)
+        self.num_ineqconstraints, self.num_eqconstraints = N, 0
+        self.ineqconstraints_all = [(lambda x, i=i: -x.ravel()[i] - lb) for i in range(N)]
+        self.ineqconstraints_riemannian_gradient = lambda i: (lambda x: M.projection(x, unit(i)))
+        self.ineqconstraints_riemannian_gradient_all = [self.ineqconstraints_riemannian_gradient(i) for i in range(N)]
+        self.ineqconstraints_riemannian_hessian_all = [(lambda x, v, i=i: -v @ (x.T @ unit(i))) for i in range(N)]
+        self.eqconstraints_all = []
+        self.eqconstraints_riemannian_gradient_all = []
+        self.eqconstraints_riemannian_hessian_all = []
+
+
+_PROBE_EVAL = {"cost": 1.0, "distance": 0.0, "residual": 1.0, "gradnorm": 1.0, "complviolation": 0.0,
+               "dualviolation": 0.0, "manviolation": 0, "maxviolation": 0.0, "meanviolation": 0.0}
+
+
+def _callback_probes():
+    """Two points of Grassmann(3, 1) (k = 1: X^T G_L is a number, so the reference's own function does
+    not depend on its basis draw): none of the constraints active, and the first one active."""
+    lb = LB
+    free = np.array([[0.48], [0.6], [0.64]])
+    edge = np.array([[-lb], [0.6], [math.sqrt(1.0 - 0.36 - lb * lb)]])
+    y = np.array([0.7, 0.2, 1.3])
+    return [(_CallbackProbeProblem(3, 1, 10.0, lb), x, y) for x in (free, edge)]
+
+
+def rosenbrock_callback_kind(f) -> int:
+    """Classify 'callbackfun', in the style of ``rosenbrock_manvio_kind``: CALLBACK_NONE for None or a
+    callback that returns ``eval`` unchanged (the reference's default), CALLBACK_SECOND_ORDER for this
+    module's ``callbackfun`` or any function that, on the probe points, adds exactly the keys
+    ``second_order_residual`` and ``condition_number`` with the probe's symmetric-part values (1e-8
+    relative) -- the reference's own (src/Rosenbrock/simulator.py:100-105) does.  Anything else cannot
+    run on the device and raises NotImplementedError."""
+    if f is None:
+        return CALLBACK_NONE
+    if f is callbackfun:
+        return CALLBACK_SECOND_ORDER
+    import contextlib
+    import io
+    no = NotImplementedError("callbackfun must be None, return eval unchanged, or be the Rosenbrock simulator's "
+                             "second-order residual (src/Rosenbrock/simulator.py:100-105); arbitrary Python "
+                             "callables cannot run on the device")
+    kinds = []
+    for probe, x, y in _callback_probes():
+        ev = dict(_PROBE_EVAL)
+        try:
+            with contextlib.redirect_stdout(io.StringIO()):
+                try:
+                    out = f(probe, x.copy(), y.copy(), [], dict(ev))
+                except TypeError:   # base_solver.py:26's four-argument default
+                    out = f(probe, x.copy(), {}, dict(ev))
+        except Exception as e:
+            raise no from e
+        if not isinstance(out, dict):
+            raise no
+        if out == ev:
+            kinds.append(CALLBACK_NONE)
+            continue
+        if set(out) != set(ev) | {"second_order_residual", "condition_number"} or any(out[q] != ev[q] for q in ev):
+            raise no
+        lo, cond = symmetric_second_order(probe.n, probe.k, probe.alpha, probe.lb, x, y)
+        close = lambda a, b: a is not None and b is not None and abs(a - b) <= 1e-8 * abs(b)
+        if not (close(out["second_order_residual"], lo) and close(out["condition_number"], cond)):
+            raise no
+        kinds.append(CALLBACK_SECOND_ORDER)
+    if len(set(kinds)) != 1:
+        raise no
+    return kinds[0]
+
+
 def _has(cfg, key):
     return (key in cfg) if isinstance(cfg, dict) else hasattr(cfg, key)
 
@@ -163,6 +346,7 @@ class RosenbrockBatch:
         self._keep: List[torch.Tensor] = []
         self.ro: Optional[ResolvedOptions] = None
         self._bound = False
+        self.trail: Optional[torch.Tensor] = None
 
     def _view(self, kind: int, shape):
         off = int(self.lib.riptrm_gr_workspace_offset(self.n, self.k, self.batch, self.cap, kind))
@@ -217,6 +401,7 @@ class RosenbrockBatch:
                                                self.ws_bytes, self.cap), "riptrm_gr_bind")
         self._prob = pr
         self._bound = True
+        self.trail = None   # riptrm_gr_bind unbinds the trail
         return self
 
     def _mat(self, a) -> torch.Tensor:
@@ -269,9 +454,87 @@ class RosenbrockBatch:
                        "riptrm_gr_launch_info")
         return {"lds_bytes": int(a.value), "threads": int(b.value), "workgroups_per_cu": int(c.value)}
 
+    def second_order(self, x, y, active_tol=ACTIVE_TOL, linindtol=LININDTOL, barrier=False, mu=None,
+                     inst=None) -> Dict[str, np.ndarray]:
+        """The second-order residual at every point (x_p, y_p) in one launch (``riptrm_gr_second_order``).
+        x: (npoints, n, k), y: (npoints, n k), numpy or tensors on the device; active_tol: a scalar or
+        one per point; inst: the bound instance (alpha, lb) of every point, default point p = instance p.
+        barrier: HwCur (RIPTRM.py:729) instead of the Lagrangian's Hessian.  Returns arrays per point:
+        mineig, maxeig, cond (NaN where nulldim == 0), nulldim, nactive, nindep, info."""
+        if not self._bound:
+            raise RuntimeError("second_order: load() first")
+        d = self.k * (self.n - self.k)
+        if d > C["RIPTRM_TRS_DIM_MAX"]:
+            raise NotImplementedError(f"second_order needs manifold dimension k (n - k) <= {C['RIPTRM_TRS_DIM_MAX']} "
+                                      f"(got {d} at n = {self.n}, k = {self.k})")
+        x = x if isinstance(x, torch.Tensor) else np.asarray(x, dtype=np.float64)
+        y = y if isinstance(y, torch.Tensor) else np.asarray(y, dtype=np.float64)
+        P = int(x.shape[0])
+        X, Y = self._dev(x.reshape(P, self.N), (P, self.N)), self._dev(y.reshape(P, self.N), (P, self.N))
+        tol = np.asarray(active_tol, dtype=np.float64)
+        if tol.ndim != 0 and tol.shape != (P,):
+            raise ValueError(f"active_tol must be a scalar or of shape ({P},)")
+        told = self._dev(tol, (1,) if tol.ndim == 0 else (P,))
+        keep = [X, Y, told]
+        instp = None
+        if inst is not None:
+            ia = np.asarray(inst.cpu() if isinstance(inst, torch.Tensor) else inst, dtype=np.int64)
+            if ia.shape != (P,) or (P and (ia.min() < 0 or ia.max() >= self.batch)):
+                raise ValueError(f"inst must hold {P} instance indices in [0, {self.batch})")
+            it = torch.as_tensor(ia.astype(np.int32)).to(self.device)
+            keep.append(it)
+            instp = ctypes.c_void_p(it.data_ptr())
+        elif P > self.batch:
+            raise ValueError(f"{P} points for {self.batch} bound instances: pass inst")
+        mup = None
+        if barrier and mu is not None:
+            mud = self._dev(np.asarray(mu, dtype=np.float64), (P,))
+            keep.append(mud)
+            mup = ctypes.c_void_p(mud.data_ptr())
+        nf = C["RIPTRM_GR_SO_NFIELDS"]
+        out = torch.zeros((P, nf), dtype=torch.float64, device=self.device)
+        self.ctx.set_stream(_stream_handle(self.device))
+        self.ctx.check(self.lib.riptrm_gr_second_order(
+            self.ctx.h, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()), self.N, instp, P,
+            ctypes.c_void_p(told.data_ptr()), 0 if tol.ndim == 0 else 1, float(linindtol), 1 if barrier else 0, mup,
+            ctypes.c_void_p(out.data_ptr())), "riptrm_gr_second_order")
+        torch.cuda.synchronize(self.device)
+        o = out.cpu().numpy()
+        res = {name: o[:, C[f"RIPTRM_GR_SO_{name.upper()}"]].copy() for name in ("mineig", "maxeig", "cond")}
+        for name in ("nulldim", "nactive", "nindep", "info"):
+            col = o[:, C[f"RIPTRM_GR_SO_{name.upper()}"]]
+            res[name] = np.where(np.isnan(col), -1, col).astype(np.int64)
+        return res
+
+    def bind_trail(self) -> "RosenbrockBatch":
+        """Keep the (x, y) of every log record of the next solves (``riptrm_gr_bind_trail``)."""
+        nbytes = int(self.lib.riptrm_gr_trail_bytes(self.n, self.k, self.batch, self.cap))
+        self.trail = torch.zeros((self.batch, self.cap, 2, self.N), dtype=torch.float64, device=self.device)
+        assert self.trail.numel() * 8 == nbytes
+        self.ctx.check(self.lib.riptrm_gr_bind_trail(self.ctx.h, ctypes.c_void_p(self.trail.data_ptr()), nbytes),
+                       "riptrm_gr_bind_trail")
+        return self
+
+    def trail_points(self, st: np.ndarray):
+        """(x, y, inst) of the trail's valid slots in the chronological order of ``assemble_log``, every
+        instance's rows one after another, and the row count per instance: torch indexing, on the device."""
+        count = st[:, C["RIPTRM_STAT_LOG_COUNT"]].astype(np.int64)
+        cap = min(self.cap, int(self.ro.c_opt.log_capacity))
+        bi, si, rows = [], [], []
+        for b in range(self.batch):
+            order, _ = assemble_log(np.arange(self.cap), int(count[b]), cap)
+            bi.append(np.full(len(order), b, dtype=np.int64))
+            si.append(np.asarray(order, dtype=np.int64))
+            rows.append(len(order))
+        bi, si = np.concatenate(bi), np.concatenate(si)
+        pts = self.trail[torch.as_tensor(bi, device=self.device), torch.as_tensor(si, device=self.device)]
+        return pts[:, 0].contiguous(), pts[:, 1].contiguous(), bi, rows
+
     def begin(self, x0, y0, option: Dict[str, Any], restart_every: int = 0) -> ResolvedOptions:
         ro = resolve_options(option, math.sqrt(self.k), self.cap, restart_every,
-                             manvio_classifier=rosenbrock_manvio_kind)
+                             manvio_classifier=rosenbrock_manvio_kind, callback_classifier=rosenbrock_callback_kind)
+        if ro.callback_kind and self.trail is None:
+            self.bind_trail()
         if ro.exact:
             raise NotImplementedError("TRS_solver='Exact_RepMat' is not implemented for the Rosenbrock problem on "
                                       "Grassmann(n, k): the reference's tangent basis there is a draw of "
@@ -302,5 +565,14 @@ class RosenbrockBatch:
             rows, drop = assemble_log(slots[b], int(count[b]), cap)
             logs.append(rows.copy())
             dropped.append(drop)
+        cb = None
+        if self.ro.callback_kind == CALLBACK_SECOND_ORDER:   # one launch over every row of every instance
+            X, Y, inst, rows = self.trail_points(st)
+            so = self.second_order(X, Y, inst=inst)
+            cols = second_order_columns(so)
+            cb, at = [], 0
+            for r in rows:
+                cb.append({key: val[at:at + r] for key, val in cols.items()})
+                at += r
         return BatchResult(x=self.x().clone(), y=self.y().clone(), stats=st, raw_log=logs, ro=self.ro,
-                           dropped=np.array(dropped))
+                           dropped=np.array(dropped), callback_cols=cb)
