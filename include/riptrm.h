@@ -534,7 +534,8 @@ int riptrm_gr_tcg(riptrm_ctx* ctx, const riptrm_options* opt, const double* x, c
  * numpy.linalg.matrix_rank(x) == k else 0 (batch int32).  Asynchronous. */
 int riptrm_gr_ops(riptrm_ctx* ctx, const double* x, const double* u, const double* y, double* proj,
                   double* retr, double* dist, int32_t* fullrank);
-/* Whole RIPTRM solves (RIPTRM.py:909-976, TRS_solver tCG only) from x0, y0 (batch x n k); tables as in
+/* Whole RIPTRM solves (RIPTRM.py:909-976; TRS_solver tCG, or Exact_RepMat as described under "Exact_RepMat in
+ * the pinned frame" below) from x0, y0 (batch x n k); tables as in
  * riptrm_solve_begin.  One launch, asynchronous: synchronise the stream, then read the workspace.  An
  * instance whose log-barrier value, ared / pred, tCG residual or step norm is not finite stops with
  * RIPTRM_ERR_NONFINITE at the start of its outer step; the others go on. */
@@ -581,6 +582,33 @@ int riptrm_gr_second_order(riptrm_ctx* ctx, const double* x, const double* y, in
  * riptrm_gr_bind unbinds too.  With no trail bound the solve launches the kernel it always did. */
 int64_t riptrm_gr_trail_bytes(int32_t n, int32_t k, int32_t batch, int32_t log_capacity);
 int riptrm_gr_bind_trail(riptrm_ctx* ctx, void* trail, int64_t bytes);
+
+/* ---- Exact_RepMat in the pinned frame (RIPTRM.py:433-444, :599-617) -----------------------------------
+ * riptrm_gr_solve also takes opt->trs_solver = RIPTRM_TRS_SOLVER_EXACT_REPMAT (with or without
+ * second_order_stationarity and a bound trail) when 1 <= k (n - k) <= riptrm_gr_exact_dim_max(); above that
+ * it returns RIPTRM_E_ARG.  The tangent basis is fixed: with the Householder QR X = Q [R; 0] (reflector j
+ * built from column j below the diagonal, ahat_j = -||w|| if w_j >= 0 else +||w||, i.e. LAPACK's sign), basis
+ * vector a k + b (0 <= a < n - k, 0 <= b < k) is Q e_{k+a} e_b^T.  The matrix is the reference's own:
+ * A[i][j] = <b_i, HwCur(b_j)> for i <= j, mirrored (utils.py:565-573) -- HwCur is not self-adjoint on this
+ * problem, so that is not the symmetric part and it depends on the frame and its order.  Per inner step the
+ * matrix is built at the iterate (and, with second_order_stationarity, once more at the trial point: the
+ * reference's reuse of HwNewmatrix is recomputed, the frame being deterministic), RIPTRM_STAT_PASSES counts
+ * the k (n - k) operator applications of each; the tCG counters stay 0 and RIPTRM_STAT_TCG_LAST_STOP holds
+ * the RIPTRM_TRS_* type.  A non-finite matrix entry, linear term or direction stops that instance with
+ * RIPTRM_ERR_NONFINITE, non-finite eigenvalues with RIPTRM_ERR_EIGEN; the others go on. */
+/* The largest manifold dimension k (n - k) of the Exact_RepMat path: the subproblem's LDS work area next to the
+ * solve's own vectors within one workgroup's 160 KiB, at the three waves every admitted shape fits. */
+int32_t riptrm_gr_exact_dim_max(void);
+/* Dynamic LDS bytes of the Exact_RepMat workgroup of shape (n, k); -1 outside the limits. */
+int64_t riptrm_gr_exact_lds_bytes(int32_t n, int32_t k);
+/* The pieces of one Exact_RepMat step at (x_b, y_b, mu_b, Delta_b) of the bound batch, all device pointers:
+ * A (batch x d x d, d = k (n - k), row-major) and a (batch x d) the matrix and the coordinates of cxCur,
+ * dx (batch x n k) the direction, kind (batch) its RIPTRM_TRS_* type -- or RIPTRM_TCG_NONFINITE /
+ * RIPTRM_TCG_EIGFAIL, dx then 0 --, lam1 (batch) TRSgep's multiplier, mineig (batch) the smallest eigenvalue
+ * of A (NaN if it has none).  stats RIPTRM_STAT_PASSES = the operator applications.  Asynchronous. */
+int riptrm_gr_exact(riptrm_ctx* ctx, double tolhardcase, const double* x, const double* y, const double* mu,
+                    const double* delta, double* A, double* a, double* dx, int32_t* kind, double* lam1,
+                    double* mineig);
 
 #ifdef __cplusplus
 }

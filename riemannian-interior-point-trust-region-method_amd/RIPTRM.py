@@ -15,8 +15,14 @@ eqLagmult)`` whose ``log`` has the reference's columns, one row per inner iterat
 * the problem is a structured descriptor (``problems.NonnegPCAProblem``, ``si.SIProblem`` for
   StableIdentification or ``rosenbrock.RosenbrockProblem`` for Rosenbrock on Grassmann(n, k)) instead
   of a list of autograd closures, because closures cannot execute on the GPU;
-* Rosenbrock runs with ``TRS_solver='tCG'`` (what its config selects); ``'Exact_RepMat'`` raises for
-  it: the reference's tangent basis there is a draw of ``random_tangent_vector``;
+* Rosenbrock runs with ``TRS_solver='tCG'`` (what its config selects).  ``'Exact_RepMat'`` is opt-in
+  there through the reference's own key: with ``basisfun=rosenbrock.basisfun`` (or any callable that
+  reproduces that frame: the Householder QR X = Q [R; 0] in LAPACK's sign convention, vector a k + b =
+  Q e_{k+a} e_b^T) the solve runs on the device for manifold dimension k (n - k) up to
+  ``RosenbrockBatch.exact_dim_max()`` (91), with ``second_order_stationarity`` and the callback below.
+  With ``basisfun`` None (the reference's default draw of ``random_tangent_vector``) or any other basis it
+  raises: the operator is not self-adjoint on this problem, so the reference's matrix and step depend on
+  the basis (DESIGN.md 7e).  ``basisfun`` stays ignored for NonnegPCA and StableIdentification;
 * ``manviofun`` must be 0 or the problem's simulator function (NonnegPCA ``||x|| - 1``,
   StableIdentification's symmetry / definiteness violation, Rosenbrock's rank test);
   ``callbackfun`` must be None or return ``eval`` unchanged, except for Rosenbrock, where the simulator's
@@ -45,8 +51,8 @@ import torch
 
 from engine import NonnegPCABatch, REFERENCE_DEFAULTS, manvio_kind, resolve_options
 from problems import NonnegPCAProblem
-from rosenbrock import (CALLBACK_NONE, RosenbrockBatch, RosenbrockProblem, rosenbrock_callback_kind,
-                        rosenbrock_manvio_kind)
+from rosenbrock import (CALLBACK_NONE, RosenbrockBatch, RosenbrockProblem, rosenbrock_basis_kind,
+                        rosenbrock_callback_kind, rosenbrock_manvio_kind)
 from si import SIBatch, SIProblem, si_manvio_kind
 from solver_base import Output, Solver
 
@@ -182,9 +188,9 @@ class RIPTRM(Solver):
         if any((p.n, p.k) != (n, k) for p in problems):
             raise ValueError("run_batch needs Rosenbrock problems of equal (n, k)")
         if self.option['TRS_solver'] != 'tCG':
-            raise NotImplementedError("TRS_solver='Exact_RepMat' is not implemented for the Rosenbrock problem on "
-                                      "Grassmann(n, k): the reference's tangent basis there is a draw of "
-                                      "random_tangent_vector, so parity is unpinned; use TRS_solver='tCG'")
+            # opt-in through the reference's own key: only the pinned frame makes its matrix well defined
+            # (raises NotImplementedError for None, a drawn basis or any other frame)
+            rosenbrock_basis_kind(self.option.get('basisfun'))
         B = len(problems)
         if self.callback_kind != CALLBACK_NONE:
             from engine import C

@@ -33,6 +33,12 @@
 // positive definite G it yields G = V L V^T (G V has orthogonal columns of norms L); for X^T Y and for X
 // itself (the rank test of src/Rosenbrock/simulator.py:107-114) it yields the singular values directly
 // rather than through the eigenvalues of C^T C, which would square away the digits arccos needs.
+//
+// Exact_RepMat (RIPTRM.py:433-444, :599-617) is the EXACT instantiation of the same engine, k_gr_exact: in
+// place of tcg() it builds the matrix of HwCur in the pinned Householder frame of X (rosenbrock.basisfun; the
+// reference's upper-triangle mirror, which on this problem depends on the frame) and calls the LDS subproblem
+// solver of riptrm_trs.h; with second_order_stationarity the same matrix at the trial point gives
+// mineigvalHw.  The tCG kernels k_gr are compiled as they were (DESIGN.md 7e has the resource table).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <cstring>
@@ -52,7 +58,7 @@ constexpr int KK = KMAX * KMAX;
 
 typedef riptrm_trs::lds_f64 lf;
 
-enum Mode : int { MODE_SOLVE = 0, MODE_HVP = 1, MODE_TCG = 2, MODE_OPS = 3 };
+enum Mode : int { MODE_SOLVE = 0, MODE_HVP = 1, MODE_TCG = 2, MODE_OPS = 3, MODE_EXACT = 4 };
 
 struct GRParams {
   int32_t n, k, batch, cap, mode, tab_len;
@@ -81,6 +87,12 @@ struct GRParams {
   const double* tolL_tab;
   const double* tolC_tab;
   riptrm_options opt;
+  // MODE_EXACT outputs (riptrm_gr_exact); out_v takes dx
+  double* out_A;        // batch x d x d
+  double* out_a;        // batch x d
+  double* out_lam;      // batch
+  double* out_mineig;   // batch
+  int32_t* out_kind;    // batch  RIPTRM_TRS_*, or RIPTRM_TCG_NONFINITE / RIPTRM_TCG_EIGFAIL
 };
 
 struct Layout {
@@ -106,6 +118,26 @@ inline Layout make_layout(int n, int k, int batch, int cap) {
 __host__ __device__ constexpr int gr_threads(int N) { return (N + 63) / 64 * 64; }
 __host__ __device__ constexpr int gr_lds_doubles(int NT) { return NVEC * NT + 4 * KK + KMAX + 2 * (NT / 64); }
 
+// ---- Exact_RepMat (the EXACT instantiation) -------------------------------------------------------
+// The subproblem's work area (riptrm_trs::work_doubles(d): the matrix, its eigenvectors, the vectors
+// and the Jacobi rotation table) sits behind k_gr's own area and the frame's 2 KMAX scalars (column
+// dots, reflector scales).  The frame's reflectors, the frame vector and its image take R, DEL and
+// HETA, which only tCG uses.  d <= RIPTRM_TRS_DIM_MAX and k <= KMAX give n k = d + k^2 <= 160: three
+// waves at most, and the limit on d is what fits one workgroup's 160 KiB at that width.
+constexpr int LDS_LIMIT = 160 * 1024;
+constexpr int EXACT_NT_MAX = 192;
+static_assert(riptrm_trs::DIM_MAX + KK <= EXACT_NT_MAX, "n k = d + k^2 must fit EXACT_NT_MAX threads");
+__host__ __device__ constexpr int gr_exact_lds_doubles(int NT, int d) {
+  return gr_lds_doubles(NT) + 2 * KMAX + riptrm_trs::work_doubles(d);
+}
+constexpr int exact_dim_max() {
+  int d = 0;
+  while (d < riptrm_trs::DIM_MAX && (int64_t)gr_exact_lds_doubles(EXACT_NT_MAX, d + 1) * 8 <= LDS_LIMIT) ++d;
+  return d;
+}
+constexpr int EXACT_DMAX = exact_dim_max();
+static_assert(EXACT_DMAX >= 80, "every shape with k (n - k) <= 80 must fit");
+
 // numpy.minimum / numpy.maximum (NaN-propagating), RIPTRM.py:681-683
 __device__ __forceinline__ double np_min(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b < a ? b : a); }
 __device__ __forceinline__ double np_max(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b > a ? b : a); }
@@ -114,7 +146,7 @@ struct Info {  // inner-iteration record of solver_status (RIPTRM.py:986-1023)
   double has, num, status, tr, dxtype, normdx, minx, miny, compl_, hasratio, ratio, ru, dc;
 };
 
-template <int NT, bool TRAIL>
+template <int NT, bool TRAIL, bool EXACT = false>
 struct Eng {
   const GRParams& P;
   const int b, l, n, k, N, kk;
@@ -125,6 +157,11 @@ struct Eng {
   lf *M1, *M2, *MG, *VV;   // KMAX x KMAX factors (row stride k)
   lf *SIG;                 // KMAX singular values
   riptrm_trs::Blk<NT> blk;
+  // EXACT only: the frame (reflectors of X's QR in REF = R, scales BETA, column dots CW), the frame
+  // vector FV = DEL and its image FH = HETA, the subproblem's work area, the row's mineigvalHw
+  lf *REF, *FV, *FH, *CW, *BETA;
+  double* trs_lds;
+  double so_has = 0.0, so_min = 0.0;
 
   __device__ __forceinline__ Eng(const GRParams& P_, int b_, double* lds)
       : P(P_), b(b_), l((int)threadIdx.x), n(P_.n), k(P_.k), N(P_.n * P_.k), kk(P_.k * P_.k),
@@ -137,6 +174,9 @@ struct Eng {
     W2 = base + 12 * NT;
     lf* f = base + NVEC * NT;
     M1 = f; M2 = f + KK; MG = f + 2 * KK; VV = f + 3 * KK; SIG = f + 4 * KK;
+    REF = R; FV = DEL; FH = HETA;
+    CW = base + gr_lds_doubles(NT); BETA = CW + KMAX;
+    trs_lds = lds + gr_lds_doubles(NT) + 2 * KMAX;
     alpha = P.alpha[(int64_t)b * P.alpha_stride];
     lb = P.lb[(int64_t)b * P.lb_stride];
   }
@@ -410,6 +450,129 @@ struct Eng {
     return stop;
   }
 
+  // ---- Exact_RepMat, RIPTRM.py:433-444 and :599-617, in the pinned frame ---------------------------
+  // The frame (rosenbrock.basisfun; the arithmetic of riptrm_grassmann_so.hip::qr_frame): Householder QR
+  // X = Q [R; 0], vector a k + b = Q e_{k+a} e_b^T; the coordinates of a horizontal U are rows k.. of
+  // Q^T U, coordinate c = element k k + c of the row-major layout.  X visible
+  __device__ __forceinline__ void qr_frame() {
+    W1[l] = act ? X[l] : 0.0;
+    REF[l] = 0.0;
+    __syncthreads();
+    for (int j = 0; j < k; ++j) {
+      const double w = W1[l];
+      const double nrm = sqrt(bsum((act && lj == j && li >= j) ? w * w : 0.0));
+      const double xjj = W1[j * k + j];
+      const double ah = xjj >= 0.0 ? -nrm : nrm;
+      const double beta = nrm > 0.0 ? 1.0 / (nrm * (nrm + fabs(xjj))) : 0.0;   // 2 / (v^T v)
+      __syncthreads();
+      if (act && lj == j && li >= j) REF[l] = (li == j) ? xjj - ah : w;
+      if (l == 0) BETA[j] = beta;
+      __syncthreads();
+      if (l < k) {
+        double acc = 0.0;
+        if (l > j)
+          for (int i = j; i < n; ++i) acc = acc + REF[i * k + j] * W1[i * k + l];
+        CW[l] = acc;
+      }
+      __syncthreads();
+      if (act && lj > j && li >= j) W1[l] = w - (beta * CW[lj]) * REF[li * k + j];
+      __syncthreads();
+    }
+  }
+  // U <- H_j U for reflector j (U n x k, in place).  U visible before and after
+  __device__ __forceinline__ void reflect(lf* U, int j) {
+    if (l < k) {
+      double acc = 0.0;
+      for (int i = j; i < n; ++i) acc = acc + REF[i * k + j] * U[i * k + l];
+      CW[l] = acc;
+    }
+    __syncthreads();
+    if (act && li >= j) U[l] = U[l] - (BETA[j] * CW[lj]) * REF[li * k + j];
+    __syncthreads();
+  }
+  __device__ __forceinline__ void apply_qt(lf* U) {   // U <- Q^T U
+    for (int j = 0; j < k; ++j) reflect(U, j);
+  }
+  __device__ __forceinline__ void apply_q(lf* U) {    // U <- Q U
+    for (int j = k - 1; j >= 0; --j) reflect(U, j);
+  }
+  // selfadj_operator2matrix (utils.py:565-573) of HwCur at the prepared point (X, Y, S, X^T G_L) in the
+  // frame of X: A[i][j] = <b_i, HwCur(b_j)> for i <= j, mirrored -- not the symmetric part; with want_a
+  // the coordinates of c too (RIPTRM.py:438-440).  Returns false if an entry is not finite
+  __device__ __forceinline__ bool repmat(riptrm_trs::Work& w, bool want_a, double& hvps) {
+    const int d = w.dim, lda = w.lda;
+    qr_frame();
+    for (int j = 0; j < d; ++j) {
+      FV[l] = (l == kk + j) ? 1.0 : 0.0;
+      __syncthreads();
+      apply_q(FV);
+      hw(FH, FV);
+      hvps += 1.0;
+      apply_qt(FH);
+      if (act && l >= kk && l - kk <= j) {
+        const double v = FH[l];
+        w.A[(l - kk) * lda + j] = v;
+        w.A[j * lda + (l - kk)] = v;
+      }
+      __syncthreads();
+    }
+    double bad = 0.0;
+    for (int e = l; e < d * d; e += NT)
+      if (!isfinite(w.A[(e / d) * lda + e % d])) bad = 1.0;
+    if (want_a) {
+      FH[l] = act ? C[l] : 0.0;
+      __syncthreads();
+      apply_qt(FH);
+      if (act && l >= kk) {
+        const double v = FH[l];
+        w.a[l - kk] = v;
+        if (!isfinite(v)) bad = 1.0;
+      }
+    }
+    const bool ok = !(bsum(bad) > 0.0);
+    __syncthreads();
+    return ok;
+  }
+  // compute_direction's Exact_RepMat branch at the prepared point: dx into ETA; returns RIPTRM_TRS_*,
+  // RIPTRM_TCG_NONFINITE (a matrix entry, the linear term or the solution) or RIPTRM_TCG_EIGFAIL
+  // (eigenvalues that are not finite).  lam1 (may be null) gets TRSgep's multiplier
+  __device__ __forceinline__ int trs_direction(double Delta, double& hvps, double* lam1) {
+    riptrm_trs::Work w = riptrm_trs::make_work(trs_lds, k * (n - k));
+    ETA[l] = 0.0;
+    if (!repmat(w, true, hvps)) return RIPTRM_TCG_NONFINITE;
+    const riptrm_trs::Result r = riptrm_trs::trs_solve<NT>(blk, w, Delta, P.opt.trs_tolhardcase);
+    double be = 0.0, bx = 0.0;
+    for (int i = l; i < w.dim; i += NT) {
+      if (!isfinite(w.ev[i])) be = 1.0;
+      if (!isfinite(w.x[i])) bx = 1.0;
+    }
+    be = bsum(be);
+    bx = bsum(bx);
+    if (be > 0.0) return RIPTRM_TCG_EIGFAIL;
+    if (bx > 0.0) return RIPTRM_TCG_NONFINITE;
+    ETA[l] = (act && l >= kk) ? w.x[l - kk] : 0.0;   // dx = sum_i coeff_i b_i = Q [0; coeff]
+    __syncthreads();
+    apply_q(ETA);
+    if (lam1) *lam1 = r.lam1;
+    return RIPTRM_TRS_BOUNDARY + r.kind;
+  }
+  // the smallest eigenvalue of the same matrix at the prepared point (RIPTRM.py:599-613); code = 0,
+  // RIPTRM_ERR_NONFINITE or RIPTRM_ERR_EIGEN
+  __device__ __forceinline__ double mineig_here(double& hvps, int& code) {
+    riptrm_trs::Work w = riptrm_trs::make_work(trs_lds, k * (n - k));
+    code = RIPTRM_ERR_NONE;
+    if (!repmat(w, false, hvps)) {
+      code = RIPTRM_ERR_NONFINITE;
+      return NAN;
+    }
+    const double me = riptrm_trs::min_eig<NT>(blk, w);
+    double be = 0.0;
+    for (int i = l; i < w.dim; i += NT)
+      if (!isfinite(w.ev[i])) be = 1.0;
+    if (bsum(be) > 0.0 || !isfinite(me)) code = RIPTRM_ERR_EIGEN;
+    return me;
+  }
+
   // ---- utils.py:342-368 at (X, Y); xprev = this thread's element of the previous row's point -------
   __device__ __forceinline__ void evaluation(double xprev, double (&ev)[10]) {
     const double y = act ? Y[l] : 0.0;
@@ -493,6 +656,10 @@ struct Eng {
           L[RIPTRM_LOG_ARED_PRED] = inf->ratio;
           L[RIPTRM_LOG_RADIUS_UPDATE] = inf->ru;
           L[RIPTRM_LOG_DUAL_CLIPPING] = inf->dc;
+          if constexpr (EXACT) {
+            L[RIPTRM_LOG_HAS_MINEIG] = so_has;
+            L[RIPTRM_LOG_MINEIGVALHW] = so_min;
+          }
         }
       } else {
         overflow += 1.0;
@@ -590,7 +757,17 @@ struct Eng {
           break;
         }
         int jj = 0;
-        const int tstop = tcg(Delta, jj, hvps);
+        int tstop;
+        if constexpr (EXACT) {
+          tstop = trs_direction(Delta, hvps, nullptr);
+          jj = -1;   // no tCG iterations
+          if (tstop == RIPTRM_TCG_EIGFAIL) {
+            err = RIPTRM_ERR_EIGEN;
+            break;
+          }
+        } else {
+          tstop = tcg(Delta, jj, hvps);
+        }
         tcg_total += (double)jj + 1.0;
         last_j = jj;
         last_stop = tstop;
@@ -613,10 +790,35 @@ struct Eng {
         const double compl_ = sqrt(bsum(cvv * cvv));
         info = Info{1.0, inner_it, 0.0, DeltaStep, (double)tstop, normdx, minx, miny, compl_, 0.0, 0.0, 0.0, -1.0};
         have_info = true;
+        bool mineig_ok = true;
+        if constexpr (EXACT) {
+          so_has = 0.0;
+          so_min = 0.0;
+          if (P.opt.second_order_stationarity) {   // RIPTRM.py:599-613: HwNew's matrix at (xNew, yNew)
+            // recomputed at the next step where the reference reuses HwNewmatrix (:687-692): the frame is
+            // deterministic, so the two are equal.  The operators move to the trial point and back
+            const double xc = act ? X[l] : 0.0;
+            set_point(xN, yN);
+            prepare(mu);
+            int code;
+            const double me = mineig_here(hvps, code);
+            set_point(xc, y);
+            prepare(mu);
+            if (code != RIPTRM_ERR_NONE) {
+              err = code;
+              break;
+            }
+            const double tol2 = P.opt.tol2_table ? P.opt.tol2_table[ti] : mu;
+            mineig_ok = me >= -tol2;
+            so_has = 1.0;
+            so_min = me;
+          }
+        }
         bool converged = false;
         if (xfeas) {
           const double normgl = gradlag_norm(XN, yN);
           converged = yfeas && normgl <= tolL && compl_ <= tolC;
+          if constexpr (EXACT) converged = converged && mineig_ok;
         }
         if (converged) {  // RIPTRM.py:762-766
           set_point(xN, yN);
@@ -778,6 +980,30 @@ struct Eng {
       P.out_rank[b] = fr ? 1 : 0;
     }
   }
+
+  // riptrm_gr_exact: A, a, dx, the kind and lam1 at (x, y, mu, Delta), and the smallest eigenvalue of A
+  __device__ __forceinline__ void op_exact() {
+    set_point(load(P.in_x), load(P.in_y));
+    prepare(P.in_mu[b]);
+    const int d = k * (n - k);
+    double hv = 0.0;
+    riptrm_trs::Work w = riptrm_trs::make_work(trs_lds, d);
+    const bool ok = repmat(w, true, hv);
+    for (int e = l; e < d * d; e += NT) P.out_A[(int64_t)b * d * d + e] = w.A[(e / d) * w.lda + e % d];
+    for (int e = l; e < d; e += NT) P.out_a[(int64_t)b * d + e] = w.a[e];
+    __syncthreads();
+    int code = RIPTRM_ERR_NONE;
+    const double me = ok ? mineig_here(hv, code) : NAN;
+    double lam = NAN;
+    const int kind = trs_direction(P.in_delta[b], hv, &lam);
+    store(P.out_v, act ? ETA[l] : 0.0);
+    if (l == 0) {
+      P.out_kind[b] = kind;
+      P.out_lam[b] = lam;
+      P.out_mineig[b] = code == RIPTRM_ERR_NONE ? me : NAN;
+      P.stats[(int64_t)b * RIPTRM_STAT_NFIELDS + RIPTRM_STAT_PASSES] = hv;
+    }
+  }
 };
 
 template <int NT, bool TRAIL>
@@ -790,6 +1016,18 @@ __global__ void __launch_bounds__(NT) k_gr(GRParams P) {
   else if (P.mode == MODE_HVP) e.op_hvp();
   else if (P.mode == MODE_TCG) e.op_tcg();
   else e.op_ops();
+}
+
+// The Exact_RepMat solve and its operator entry point: an instantiation of its own, so the tCG kernels
+// above compile as they always did
+template <int NT, bool TRAIL>
+__global__ void __launch_bounds__(NT) k_gr_exact(GRParams P) {
+  extern __shared__ double gr_lds[];
+  const int b = blockIdx.x;
+  if (b >= P.batch) return;
+  Eng<NT, TRAIL, true> e(P, b, gr_lds);
+  if (P.mode == MODE_SOLVE) e.solve();
+  else e.op_exact();
 }
 
 struct Bound {
@@ -860,6 +1098,30 @@ static int gr_launch(riptrm_ctx* c, const GRParams& P) {
     case 384: return gr_launch_nt<384>(c, P);
     case 448: return gr_launch_nt<448>(c, P);
     default: return gr_launch_nt<512>(c, P);
+  }
+}
+
+static bool gr_exact_ok(int n, int k) {
+  const int d = k * (n - k);
+  return d >= 1 && d <= EXACT_DMAX;
+}
+
+template <int NT>
+static int gr_launch_exact_nt(riptrm_ctx* c, const GRParams& P) {
+  const size_t shm = (size_t)gr_exact_lds_doubles(NT, P.k * (P.n - P.k)) * sizeof(double);
+  const void* fn = P.trail ? (const void*)k_gr_exact<NT, true> : (const void*)k_gr_exact<NT, false>;
+  if (shm > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+  if (P.trail) hipLaunchKernelGGL((k_gr_exact<NT, true>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+  else hipLaunchKernelGGL((k_gr_exact<NT, false>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+  HIPCHK(c, hipGetLastError());
+  return RIPTRM_OK;
+}
+
+static int gr_launch_exact(riptrm_ctx* c, const GRParams& P) {   // callers checked gr_exact_ok: n k <= 160
+  switch (gr_threads(P.n * P.k)) {
+    case 64: return gr_launch_exact_nt<64>(c, P);
+    case 128: return gr_launch_exact_nt<128>(c, P);
+    default: return gr_launch_exact_nt<EXACT_NT_MAX>(c, P);
   }
 }
 
@@ -989,8 +1251,13 @@ int riptrm_gr_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0
   if (!x0 || !y0 || !mu_table || !tolL_table || !tolC_table || table_len <= 0)
     return fail(ctx, RIPTRM_E_ARG, "gr_solve: bad argument");
   if (opt->log_capacity > ctx->gr->cap) return fail(ctx, RIPTRM_E_ARG, "gr_solve: log_capacity exceeds bound capacity");
-  if (opt->trs_solver != RIPTRM_TRS_SOLVER_TCG)
-    return fail(ctx, RIPTRM_E_ARG, "gr_solve: only TRS_solver tCG is implemented for Rosenbrock on Grassmann");
+  if (opt->trs_solver != RIPTRM_TRS_SOLVER_TCG && opt->trs_solver != RIPTRM_TRS_SOLVER_EXACT_REPMAT)
+    return fail(ctx, RIPTRM_E_ARG, "gr_solve: unknown TRS_solver");
+  const bool exact = opt->trs_solver == RIPTRM_TRS_SOLVER_EXACT_REPMAT;
+  if (exact && !gr_exact_ok(ctx->gr->prob.n, ctx->gr->prob.k))
+    return fail(ctx, RIPTRM_E_ARG, "gr_solve: Exact_RepMat needs 1 <= k (n - k) <= riptrm_gr_exact_dim_max() (" +
+                                       std::to_string(EXACT_DMAX) + "), got " +
+                                       std::to_string(ctx->gr->prob.k * (ctx->gr->prob.n - ctx->gr->prob.k)));
   HIPCHK(ctx, hipSetDevice(ctx->device));
   GRParams P = gr_params(ctx, MODE_SOLVE);
   P.opt = *opt;
@@ -1001,7 +1268,41 @@ int riptrm_gr_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0
   P.tolC_tab = tolC_table;
   P.tab_len = table_len;
   P.trail = ctx->gr->trail;   // only the solve logs: the operator entry points launch the plain kernel
-  return gr_launch(ctx, P);
+  return exact ? gr_launch_exact(ctx, P) : gr_launch(ctx, P);
+}
+
+int32_t riptrm_gr_exact_dim_max(void) { return EXACT_DMAX; }
+
+int64_t riptrm_gr_exact_lds_bytes(int32_t n, int32_t k) {
+  if (!gr_dims_ok(n, k, 1, 0) || !gr_exact_ok(n, k)) return -1;
+  return (int64_t)gr_exact_lds_doubles(gr_threads(n * k), k * (n - k)) * 8;
+}
+
+int riptrm_gr_exact(riptrm_ctx* ctx, double tolhardcase, const double* x, const double* y, const double* mu,
+                    const double* delta, double* A, double* a, double* dx, int32_t* kind, double* lam1,
+                    double* mineig) {
+  if (!ctx) return RIPTRM_E_ARG;
+  if (!ctx->gr) return fail(ctx, RIPTRM_E_STATE, "gr_exact: riptrm_gr_bind first");
+  if (!x || !y || !mu || !delta || !A || !a || !dx || !kind || !lam1 || !mineig)
+    return fail(ctx, RIPTRM_E_ARG, "gr_exact: bad argument");
+  if (!gr_exact_ok(ctx->gr->prob.n, ctx->gr->prob.k))
+    return fail(ctx, RIPTRM_E_ARG, "gr_exact: need 1 <= k (n - k) <= riptrm_gr_exact_dim_max() (" +
+                                       std::to_string(EXACT_DMAX) + "), got " +
+                                       std::to_string(ctx->gr->prob.k * (ctx->gr->prob.n - ctx->gr->prob.k)));
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  GRParams P = gr_params(ctx, MODE_EXACT);
+  P.opt.trs_tolhardcase = tolhardcase;
+  P.in_x = x;
+  P.in_y = y;
+  P.in_mu = mu;
+  P.in_delta = delta;
+  P.out_A = A;
+  P.out_a = a;
+  P.out_v = dx;
+  P.out_kind = kind;
+  P.out_lam = lam1;
+  P.out_mineig = mineig;
+  return gr_launch_exact(ctx, P);
 }
 
 int riptrm_gr_launch_info(riptrm_ctx* ctx, int32_t* lds_bytes, int32_t* threads, int32_t* wg_per_cu) {

@@ -132,6 +132,10 @@ SIGNATURES: Dict[str, tuple] = {
                                          c_double, c_int32, c_void_p, c_void_p]),
     "riptrm_gr_trail_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "riptrm_gr_bind_trail": (c_int32, [c_void_p, c_void_p, c_int64]),
+    "riptrm_gr_exact_dim_max": (c_int32, []),
+    "riptrm_gr_exact_lds_bytes": (c_int64, [c_int32, c_int32]),
+    "riptrm_gr_exact": (c_int32, [c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                  c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 

@@ -7,7 +7,10 @@ the numbers instead (``RosenbrockProblem``) and runs every RIPTRM solve of a bat
 Hydra sweep axes: alpha, the bound, start points -- inside ONE HIP launch, one workgroup per
 instance (``csrc/riptrm_grassmann.hip``: 64 ceil(n k / 64) threads, one per entry of the point,
 1 <= k <= RIPTRM_GR_KMAX, n k <= RIPTRM_GR_NKMAX).  ``TRS_solver='tCG'`` (what
-``src/Rosenbrock/config_simulation.yaml`` selects) only.  No CPU fallback.
+``src/Rosenbrock/config_simulation.yaml`` selects), and ``'Exact_RepMat'`` as an opt-in: with
+``option["basisfun"] = rosenbrock.basisfun`` (the pinned Householder frame; the reference's matrix depends on
+the basis on this problem) the exact-direction instantiation of the same kernel runs, for manifold dimension
+k (n - k) <= ``RosenbrockBatch.exact_dim_max()``; without the key it raises.  No CPU fallback.
 
 The simulator's ``callbackfun`` (``src/Rosenbrock/simulator.py:60-105``: the second-order residual and the
 condition number on every log row) runs on the device too, one workgroup per log row after the solve
@@ -297,6 +300,86 @@ def rosenbrock_callback_kind(f) -> int:
     return kinds[0]
 
 
+def householder_complement(x):
+    """Columns k.. of Q in the Householder QR X = Q [R; 0] (n x (n - k)), with the arithmetic and the sign
+    convention of ``csrc/riptrm_grassmann_so.hip::qr_frame``: reflector j is H_j = I - beta_j v_j v_j^T with
+    v_j = w - ahat e_j, w = column j of H_{j-1} .. H_0 X from row j down, ahat = -||w|| if w_j >= 0 else
+    +||w|| (LAPACK dlarfg's sign: R gets a non-positive diagonal wherever w_j >= 0), beta_j =
+    1 / (||w|| (||w|| + |w_j|)), and Q = H_0 H_1 .. H_{k-1}."""
+    x = np.asarray(x, dtype=np.float64)
+    n, k = x.shape
+    W = x.copy()
+    refl = []
+    for j in range(k):
+        w = W[j:, j].copy()
+        nrm = math.sqrt(float(np.sum(w * w)))
+        xjj = w[0]
+        ah = -nrm if xjj >= 0.0 else nrm
+        beta = 1.0 / (nrm * (nrm + abs(xjj))) if nrm > 0.0 else 0.0
+        v = np.zeros(n)
+        v[j:] = w
+        v[j] = xjj - ah
+        W[:, j + 1:] -= np.outer(v, beta * (v @ W[:, j + 1:]))
+        refl.append((v, beta))
+    E = np.eye(n)[:, k:]
+    for v, beta in reversed(refl):
+        E = E - np.outer(v, beta * (v @ E))
+    return E
+
+
+def basisfun(manifold, x):
+    """``option["basisfun"]`` with the reference's signature (src/solver/RIPTRM.py:341, :436, :603): the
+    pinned orthonormal basis of the horizontal space at x (n x k, X^T X = I) that the device uses.  Reads
+    only x.  With Q from the Householder QR X = Q [R; 0] (``householder_complement``: LAPACK's sign
+    convention, ahat_j = -sign(w_j) ||w||, sign(0) = +1), vector number a k + b (0 <= a < n - k,
+    0 <= b < k) is Q e_{k+a} e_b^T.  Deterministic, so the reference's Exact_RepMat procedure -- the
+    upper triangle of <b_i, HwCur(b_j)> mirrored (utils.py:565-573) -- is too, and the device matches it."""
+    x = np.asarray(x, dtype=np.float64)
+    n, k = x.shape
+    E = householder_complement(x)
+    eye = np.eye(k)
+    return [np.outer(E[:, a], eye[b]) for a in range(n - k) for b in range(k)]
+
+
+def _basis_probes():
+    """Two points whose frames tell the pinned basis from a draw, a permutation or another completion:
+    a generic point of Grassmann(5, 3) and one of Grassmann(4, 2) with a negative pivot."""
+    rs = np.random.RandomState(20240607)
+    a = np.linalg.qr(rs.randn(5, 3))[0]
+    b = np.linalg.qr(rs.randn(4, 2))[0]
+    if b[0, 0] > 0:
+        b = -b
+    return [a, b]
+
+
+def rosenbrock_basis_kind(f) -> int:
+    """Classify 'basisfun', in the style of ``rosenbrock_manvio_kind`` / ``rosenbrock_callback_kind``:
+    returns 1 for this module's ``basisfun`` or any callable that reproduces its frame -- every vector, in
+    order -- on the two probe points (1e-8, the callback classifier's probe tolerance; the vectors have
+    unit norm).  Anything else (None, the reference's default draw of random_tangent_vector, another
+    completion or order) raises NotImplementedError: the operator is not self-adjoint here, so the
+    reference's matrix, and with it the step, depends on the basis."""
+    no = NotImplementedError("TRS_solver='Exact_RepMat' for the Rosenbrock problem on Grassmann(n, k) needs the pinned "
+                             "tangent basis: pass basisfun=rosenbrock.basisfun (the reference's default draws "
+                             "random_tangent_vector, on which its matrix depends), or use TRS_solver='tCG'")
+    if f is None:
+        raise no
+    if f is basisfun:
+        return 1
+    for x in _basis_probes():
+        n, k = x.shape
+        try:
+            got = f(_CallbackProbeManifold(n, k), x.copy())
+            want = basisfun(None, x)
+            ok = len(got) == len(want) and all(np.shape(g) == w.shape and np.max(np.abs(np.asarray(g) - w)) <= 1e-8
+                                               for g, w in zip(got, want))
+        except Exception as e:
+            raise no from e
+        if not ok:
+            raise no
+    return 1
+
+
 def _has(cfg, key):
     return (key in cfg) if isinstance(cfg, dict) else hasattr(cfg, key)
 
@@ -506,6 +589,41 @@ class RosenbrockBatch:
             res[name] = np.where(np.isnan(col), -1, col).astype(np.int64)
         return res
 
+    def exact_dim_max(self) -> int:
+        """The largest manifold dimension k (n - k) of the Exact_RepMat path (``riptrm_gr_exact_dim_max``)."""
+        return int(self.lib.riptrm_gr_exact_dim_max())
+
+    def _check_exact_dim(self):
+        d = self.k * (self.n - self.k)
+        if not 1 <= d <= self.exact_dim_max():
+            raise NotImplementedError(f"TRS_solver='Exact_RepMat' for the Rosenbrock problem needs manifold dimension "
+                                      f"1 <= k (n - k) <= {self.exact_dim_max()} (got {d} at n = {self.n}, k = {self.k})")
+
+    def exact_step(self, x, y, mu, Delta, tolhardcase=1e-8) -> Dict[str, Any]:
+        """The pieces of one Exact_RepMat step at (x, y, mu, Delta) per instance (``riptrm_gr_exact``) in the
+        pinned frame (``basisfun``): A (batch, d, d) the mirrored-upper-triangle matrix of HwCur, a (batch, d)
+        the coordinates of cxCur, dx (batch, n, k), kind (names: 'boundary', 'interior', 'hardcase_1'), lam1,
+        mineig (the smallest eigenvalue of A) and passes (operator applications)."""
+        if not self._bound:
+            raise RuntimeError("exact_step: load() first")
+        self._check_exact_dim()
+        d = self.k * (self.n - self.k)
+        X, Y, M, D = self._mat(x), self._dev(y, (self.batch, self.N)), self._vec(mu), self._vec(Delta)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        A, a, dx = torch.zeros((self.batch, d, d), **f64), torch.zeros((self.batch, d), **f64), torch.zeros_like(X)
+        lam, me = torch.zeros(self.batch, **f64), torch.zeros(self.batch, **f64)
+        kind = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
+        self.ctx.set_stream(_stream_handle(self.device))
+        self.ctx.check(self.lib.riptrm_gr_exact(self.ctx.h, float(tolhardcase), *(ctypes.c_void_p(t.data_ptr()) for t in
+                                                                              (X, Y, M, D, A, a, dx, kind, lam, me))),
+                       "riptrm_gr_exact")
+        torch.cuda.synchronize(self.device)
+        from engine import dxtype_name
+        codes = kind.cpu().numpy()
+        return {"A": A.cpu().numpy(), "a": a.cpu().numpy(), "dx": dx.cpu().numpy(), "kind_code": codes,
+                "kind": [dxtype_name(int(c)) for c in codes], "lam1": lam.cpu().numpy(), "mineig": me.cpu().numpy(),
+                "passes": self.stats()[:, C["RIPTRM_STAT_PASSES"]].copy()}
+
     def bind_trail(self) -> "RosenbrockBatch":
         """Keep the (x, y) of every log record of the next solves (``riptrm_gr_bind_trail``)."""
         nbytes = int(self.lib.riptrm_gr_trail_bytes(self.n, self.k, self.batch, self.cap))
@@ -535,10 +653,9 @@ class RosenbrockBatch:
                              manvio_classifier=rosenbrock_manvio_kind, callback_classifier=rosenbrock_callback_kind)
         if ro.callback_kind and self.trail is None:
             self.bind_trail()
-        if ro.exact:
-            raise NotImplementedError("TRS_solver='Exact_RepMat' is not implemented for the Rosenbrock problem on "
-                                      "Grassmann(n, k): the reference's tangent basis there is a draw of "
-                                      "random_tangent_vector, so parity is unpinned; use TRS_solver='tCG'")
+        if ro.exact:   # opt-in: the reference's matrix depends on its basis here, so the basis must be the pinned one
+            rosenbrock_basis_kind(ro.option.get('basisfun'))
+            self._check_exact_dim()
         X, Y = self._mat(x0), self._dev(y0, (self.batch, self.N))
         tabs = ro.device_tables(self.device)
         self._keep = [X, Y] + tabs

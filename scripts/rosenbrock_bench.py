@@ -16,6 +16,11 @@ completed (stats OUTER_ITERS) over that time.
 CPU: tests/rosenbrock_oracle.solve (RosenbrockVectorized) on the same instances on a 16-process pool,
 wall clock around the pool's map (the pool is started and warmed before).
 Prints one JSON line; --out FILE also writes it there.  Needs the GPU: no fallback.
+
+--trs Exact_RepMat runs the same workloads with TRS_solver='Exact_RepMat', second_order_stationarity and the
+pinned frame (basisfun=rosenbrock.basisfun on the GPU, tests/rosenbrock_exact.RosenbrockExact on the CPU pool),
+both legs with inner_maxiter = 300 (under a wall clock an inner loop that does not converge would otherwise
+run to maxtime).  profiles/rosenbrock_bench_exact.json holds that leg's result; no threshold is set on it.
 """
 import argparse
 import json
@@ -32,21 +37,32 @@ for p in (ROOT, os.path.join(ROOT, "tests"), os.path.join(ROOT, "riemannian-inte
 
 BATCH, MAXITER, REPEATS, MAXTIME = 256, 8, 3, 60.0
 SHAPES = [(5, 3), (16, 4)]
+EXACT_OPTION = dict(TRS_solver="Exact_RepMat", second_order_stationarity=True, inner_maxiter=300)
 
 
 def _cpu_job(job):
     import rosenbrock_oracle as R
-    n, k, alpha = job
-    res = R.solve(n, k, alpha, option=dict(maxiter=MAXITER, tolresid=0.0, maxtime=MAXTIME))
+    n, k, alpha, exact = job
+    option = dict(maxiter=MAXITER, tolresid=0.0, maxtime=MAXTIME)
+    if exact:
+        import rosenbrock_exact as X
+        from oracle.riptrm_oracle import RIPTRMOracle
+        option.update(EXACT_OPTION)
+        x0, y0 = R.initial_point(n, k)
+        res = RIPTRMOracle(R._option(k, option)).run(X.RosenbrockExact(n, k, alpha), x0, y0)
+    else:
+        res = R.solve(n, k, alpha, option=option)
     return res.outer_iterations, res.inner_iterations, str(res.stoppingcriterion).startswith("Max time")
 
 
-def gpu_leg(n, k, alphas):
+def gpu_leg(n, k, alphas, exact=False):
     import torch
     import rosenbrock
     eng = rosenbrock.RosenbrockBatch(n, k, len(alphas), log_capacity=64).load(alphas)
     opt = {"TRS_solver": "tCG", "second_order_stationarity": False, "manviofun": rosenbrock.manviofun,
            "tolresid": 0.0, "maxtime": MAXTIME, "maxiter": MAXITER}
+    if exact:
+        opt.update(EXACT_OPTION, basisfun=rosenbrock.basisfun)
     x0 = torch.as_tensor(np.stack([np.eye(n)[:, :k]] * len(alphas))).to(eng.device).contiguous()
     y0 = torch.ones((len(alphas), n * k), dtype=torch.float64, device=eng.device)
     res = eng.solve(x0, y0, opt)   # warm-up: loads the code object
@@ -65,13 +81,16 @@ def gpu_leg(n, k, alphas):
     errors = int((res.stats[:, rosenbrock.C["RIPTRM_STAT_ERROR"]] != 0).sum())
     timed_out = int((res.stats[:, rosenbrock.C["RIPTRM_STAT_STOP_CODE"]] == rosenbrock.C["RIPTRM_STOP_MAXTIME"]).sum())
     t = float(np.median(times))
+    info = eng.launch_info()
+    if exact:   # the Exact_RepMat instantiation: its own dynamic LDS; one wave per SIMD (256 VGPRs), no occupancy query
+        info = {"lds_bytes": int(eng.lib.riptrm_gr_exact_lds_bytes(n, k)), "threads": info["threads"]}
     return {"seconds": t, "seconds_all": times, "outer_iterations": outer, "inner_iterations": inner,
             "outer_it_per_s": outer / t, "inner_it_per_s": inner / t, "instances_with_error": errors,
-            "instances_stopped_by_maxtime": timed_out, **eng.launch_info()}
+            "instances_stopped_by_maxtime": timed_out, **info}
 
 
-def cpu_leg(pool, n, k, alphas):
-    jobs = [(n, k, float(a)) for a in alphas]
+def cpu_leg(pool, n, k, alphas, exact=False):
+    jobs = [(n, k, float(a), exact) for a in alphas]
     t0 = time.perf_counter()
     out = pool.map(_cpu_job, jobs, chunksize=1)
     t = time.perf_counter() - t0
@@ -86,25 +105,33 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--out", default=None, help="also write the JSON line to this file")
     ap.add_argument("--procs", type=int, default=16, help="CPU pool size")
+    ap.add_argument("--trs", default="tCG", choices=["tCG", "Exact_RepMat"], help="TRS_solver of both legs")
     args = ap.parse_args()
+    exact = args.trs == "Exact_RepMat"
     import multiprocessing as mp
     if not os.path.exists("/dev/kfd"):
         raise SystemExit("rosenbrock_bench needs the GPU")
     alphas = np.logspace(0, 7, BATCH)
     # the pool forks, and finishes, before this process touches the GPU
     pool = mp.get_context("fork").Pool(args.procs)
-    pool.map(_cpu_job, [(5, 3, 1.0)] * args.procs, chunksize=1)   # warm the workers (imports)
+    pool.map(_cpu_job, [(5, 3, 1.0, exact)] * args.procs, chunksize=1)   # warm the workers (imports)
     result = {"metric": "outer RIPTRM iterations/s, Rosenbrock on Grassmann(n, k), 256 instances, one launch",
               "batch": BATCH, "maxiter": MAXITER, "maxtime_s": MAXTIME, "alpha": "logspace(0, 7, 256)", "dtype": "f64",
               "cpu_pool_processes": args.procs, "shapes": {}}
-    cpu = {s: cpu_leg(pool, s[0], s[1], alphas) for s in SHAPES}
+    if exact:
+        result.update(TRS_solver=args.trs, second_order_stationarity=True, inner_maxiter=EXACT_OPTION["inner_maxiter"],
+                      basisfun="rosenbrock.basisfun")
+    cpu = {}
+    for s in SHAPES:
+        cpu[s] = cpu_leg(pool, s[0], s[1], alphas, exact)
+        print(f"[rosenbrock_bench] CPU pool {s}: {cpu[s]['seconds']:.1f} s", file=sys.stderr, flush=True)
     pool.close()
     pool.join()
     import torch
     if not torch.cuda.is_available():
         raise SystemExit("rosenbrock_bench needs the GPU")
     for (n, k) in SHAPES:
-        g = gpu_leg(n, k, alphas)
+        g = gpu_leg(n, k, alphas, exact)
         c = cpu[(n, k)]
         result["shapes"][f"{n}x{k}"] = {"gpu": g, "cpu_pool": c,
                                         "gpu_over_cpu_pool": g["outer_it_per_s"] / c["outer_it_per_s"],
