@@ -18,8 +18,8 @@ eqLagmult)`` whose ``log`` has the reference's columns, one row per inner iterat
 * Rosenbrock runs with ``TRS_solver='tCG'`` (what its config selects).  ``'Exact_RepMat'`` is opt-in
   there through the reference's own key: with ``basisfun=rosenbrock.basisfun`` (or any callable that
   reproduces that frame: the Householder QR X = Q [R; 0] in LAPACK's sign convention, vector a k + b =
-  Q e_{k+a} e_b^T) the solve runs on the device for manifold dimension k (n - k) up to
-  ``RosenbrockBatch.exact_dim_max()`` (91), with ``second_order_stationarity`` and the callback below.
+  Q e_{k+a} e_b^T; on the device csrc/riptrm_grassmann_ops.h::qr_frame) the solve runs on the device for
+  manifold dimension k (n - k) up to ``RosenbrockBatch.exact_dim_max()`` (91), with ``second_order_stationarity`` and the callback below.
   With ``basisfun`` None (the reference's default draw of ``random_tangent_vector``) or any other basis it
   raises: the operator is not self-adjoint on this problem, so the reference's matrix and step depend on
   the basis (DESIGN.md 7e).  ``basisfun`` stays ignored for NonnegPCA and StableIdentification;

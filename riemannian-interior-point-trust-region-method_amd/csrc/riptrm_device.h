@@ -96,6 +96,11 @@ __host__ __device__ inline int64_t log_slot(int64_t k, int64_t cap) {
   const int64_t h = cap / 2, t = cap - h;
   return h + (k - h) % t;
 }
+
+// numpy.minimum / numpy.maximum (NaN-propagating) used by the dual clipping (RIPTRM.py:681-683)
+__device__ __forceinline__ double np_min(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b < a ? b : a); }
+__device__ __forceinline__ double np_max(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b > a ? b : a); }
+
 inline int64_t ld_of(int32_t n) { return round_up(n > 0 ? n : 1, TS); }
 inline int64_t rows_of(int32_t n) { return round_up(n > 0 ? n : 1, 32); }  // k_pack writes 32-row sub-tiles
 inline int32_t nt_of(int32_t n) { return (int32_t)(ld_of(n) / TS); }

@@ -35,7 +35,8 @@
 // rather than through the eigenvalues of C^T C, which would square away the digits arccos needs.
 //
 // Exact_RepMat (RIPTRM.py:433-444, :599-617) is the EXACT instantiation of the same engine, k_gr_exact: in
-// place of tcg() it builds the matrix of HwCur in the pinned Householder frame of X (rosenbrock.basisfun; the
+// place of tcg() it builds the matrix of HwCur in the pinned Householder frame of X (rosenbrock.basisfun =
+// riptrm_grassmann_ops.h's Ops::qr_frame, which k_gr_so shares together with the pieces of HwCur; the
 // reference's upper-triangle mirror, which on this problem depends on the frame) and calls the LDS subproblem
 // solver of riptrm_trs.h; with second_order_stationarity the same matrix at the trial point gives
 // mineigvalHw.  The tCG kernels k_gr are compiled as they were (DESIGN.md 7e has the resource table).
@@ -46,17 +47,19 @@
 #include "riptrm_ctx.h"
 #include "riptrm_wave.h"
 #include "riptrm_trs.h"
+#include "riptrm_grassmann_ops.h"
 
 namespace riptrm_gr {
 
 #pragma clang fp contract(off)
 
-constexpr int KMAX = RIPTRM_GR_KMAX;
+using namespace riptrm_gr_dev;
+using riptrm::np_max;
+using riptrm::np_min;
+using riptrm::round_up;
+
 constexpr int NKMAX = RIPTRM_GR_NKMAX;
 constexpr int NVEC = 13;
-constexpr int KK = KMAX * KMAX;
-
-typedef riptrm_trs::lds_f64 lf;
 
 enum Mode : int { MODE_SOLVE = 0, MODE_HVP = 1, MODE_TCG = 2, MODE_OPS = 3, MODE_EXACT = 4 };
 
@@ -99,74 +102,59 @@ struct Layout {
   int64_t off_x, off_y, off_eta, off_heta, off_stats, off_log, total;
 };
 
-inline int64_t rup(int64_t a, int64_t m) { return (a + m - 1) / m * m; }
-
 inline Layout make_layout(int n, int k, int batch, int cap) {
   Layout L;
   const int64_t v = 8LL * batch * n * k;
   int64_t o = 0;
-  L.off_x = o;     o = rup(o + v, 256);
-  L.off_y = o;     o = rup(o + v, 256);
-  L.off_eta = o;   o = rup(o + v, 256);
-  L.off_heta = o;  o = rup(o + v, 256);
-  L.off_stats = o; o = rup(o + 8LL * batch * RIPTRM_STAT_NFIELDS, 256);
-  L.off_log = o;   o = rup(o + 8LL * batch * cap * RIPTRM_LOG_NFIELDS, 256);
+  L.off_x = o;     o = round_up(o + v, 256);
+  L.off_y = o;     o = round_up(o + v, 256);
+  L.off_eta = o;   o = round_up(o + v, 256);
+  L.off_heta = o;  o = round_up(o + v, 256);
+  L.off_stats = o; o = round_up(o + 8LL * batch * RIPTRM_STAT_NFIELDS, 256);
+  L.off_log = o;   o = round_up(o + 8LL * batch * cap * RIPTRM_LOG_NFIELDS, 256);
   L.total = o;
   return L;
 }
 
-__host__ __device__ constexpr int gr_threads(int N) { return (N + 63) / 64 * 64; }
 __host__ __device__ constexpr int gr_lds_doubles(int NT) { return NVEC * NT + 4 * KK + KMAX + 2 * (NT / 64); }
 
 // ---- Exact_RepMat (the EXACT instantiation) -------------------------------------------------------
 // The subproblem's work area (riptrm_trs::work_doubles(d): the matrix, its eigenvectors, the vectors
 // and the Jacobi rotation table) sits behind k_gr's own area and the frame's 2 KMAX scalars (column
 // dots, reflector scales).  The frame's reflectors, the frame vector and its image take R, DEL and
-// HETA, which only tCG uses.  d <= RIPTRM_TRS_DIM_MAX and k <= KMAX give n k = d + k^2 <= 160: three
-// waves at most, and the limit on d is what fits one workgroup's 160 KiB at that width.
-constexpr int LDS_LIMIT = 160 * 1024;
-constexpr int EXACT_NT_MAX = 192;
-static_assert(riptrm_trs::DIM_MAX + KK <= EXACT_NT_MAX, "n k = d + k^2 must fit EXACT_NT_MAX threads");
+// HETA, which only tCG uses.  The workgroup has FRAME_NT_MAX threads at most, and the limit on d is what
+// fits one workgroup's 160 KiB at that width.
 __host__ __device__ constexpr int gr_exact_lds_doubles(int NT, int d) {
   return gr_lds_doubles(NT) + 2 * KMAX + riptrm_trs::work_doubles(d);
 }
 constexpr int exact_dim_max() {
   int d = 0;
-  while (d < riptrm_trs::DIM_MAX && (int64_t)gr_exact_lds_doubles(EXACT_NT_MAX, d + 1) * 8 <= LDS_LIMIT) ++d;
+  while (d < riptrm_trs::DIM_MAX && (int64_t)gr_exact_lds_doubles(FRAME_NT_MAX, d + 1) * 8 <= LDS_LIMIT) ++d;
   return d;
 }
 constexpr int EXACT_DMAX = exact_dim_max();
 static_assert(EXACT_DMAX >= 80, "every shape with k (n - k) <= 80 must fit");
-
-// numpy.minimum / numpy.maximum (NaN-propagating), RIPTRM.py:681-683
-__device__ __forceinline__ double np_min(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b < a ? b : a); }
-__device__ __forceinline__ double np_max(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b > a ? b : a); }
 
 struct Info {  // inner-iteration record of solver_status (RIPTRM.py:986-1023)
   double has, num, status, tr, dxtype, normdx, minx, miny, compl_, hasratio, ratio, ru, dc;
 };
 
 template <int NT, bool TRAIL, bool EXACT = false>
-struct Eng {
+struct Eng : Ops {
   const GRParams& P;
-  const int b, l, n, k, N, kk;
-  const int li, lj;
-  const bool act;
-  double alpha, lb;
-  lf *X, *Y, *S, *ETA, *HETA, *R, *DEL, *HD, *C, *XN, *GL, *W1, *W2;   // NT doubles each
+  const int b;
+  lf *Y, *S, *ETA, *HETA, *R, *DEL, *HD, *C, *XN, *GL, *W2;   // NT doubles each, with Ops' X and W1
   lf *M1, *M2, *MG, *VV;   // KMAX x KMAX factors (row stride k)
   lf *SIG;                 // KMAX singular values
   riptrm_trs::Blk<NT> blk;
-  // EXACT only: the frame (reflectors of X's QR in REF = R, scales BETA, column dots CW), the frame
-  // vector FV = DEL and its image FH = HETA, the subproblem's work area, the row's mineigvalHw
-  lf *REF, *FV, *FH, *CW, *BETA;
+  // EXACT only: the frame (Ops' REF = R, BETA and CW), the frame vector FV = DEL and its image
+  // FH = HETA, the subproblem's work area, the row's mineigvalHw
+  lf *FV, *FH;
   double* trs_lds;
   double so_has = 0.0, so_min = 0.0;
 
   __device__ __forceinline__ Eng(const GRParams& P_, int b_, double* lds)
-      : P(P_), b(b_), l((int)threadIdx.x), n(P_.n), k(P_.k), N(P_.n * P_.k), kk(P_.k * P_.k),
-        li((int)threadIdx.x / P_.k), lj((int)threadIdx.x % P_.k), act((int)threadIdx.x < P_.n * P_.k),
-        blk(lds + NVEC * NT + 4 * KK + KMAX) {
+      : Ops(P_.n, P_.k), P(P_), b(b_), blk(lds + NVEC * NT + 4 * KK + KMAX) {
     lf* base = (lf*)lds;
     X = base;            Y = base + NT;       S = base + 2 * NT;    ETA = base + 3 * NT;
     HETA = base + 4 * NT; R = base + 5 * NT;   DEL = base + 6 * NT;  HD = base + 7 * NT;
@@ -186,22 +174,6 @@ struct Eng {
   __device__ __forceinline__ double bmax(double v) { return blk.max(v); }
   __device__ __forceinline__ double dot(const lf* a, const lf* c) { return bsum(act ? a[l] * c[l] : 0.0); }
 
-  // ---- the tridiagonal Hessian of f: (T u)_l, neighbours through LDS (u visible to every thread) ----
-  __device__ __forceinline__ double Tu(const lf* U) {
-    if (!act) return 0.0;
-    const double u = U[l];
-    double acc = 0.0;
-    if (l < N - 1) {
-      const double d = U[l + 1] - u;
-      acc = -2.0 * alpha * d + 2.0 * u;
-    }
-    if (l > 0) {
-      const double dm = u - U[l - 1];
-      acc = acc + 2.0 * alpha * dm;
-    }
-    return acc;
-  }
-  __device__ __forceinline__ double egrad_f(const lf* Xp) { return Tu(Xp) - ((act && l < N - 1) ? 2.0 : 0.0); }
   __device__ __forceinline__ double cost(const lf* Xp) {
     double t = 0.0;
     if (act && l < N - 1) {
@@ -211,23 +183,6 @@ struct Eng {
     return bsum(t);
   }
 
-  // ---- k x k products: M = A^T B, one thread per entry, rows in order.  A, B visible; M visible on return ----
-  __device__ __forceinline__ void xtu(lf* M, const lf* A, const lf* B) {
-    if (l < kk) {
-      const int a = l / k, c = l % k;
-      double acc = 0.0;
-      for (int i = 0; i < n; ++i) acc = acc + A[i * k + a] * B[i * k + c];
-      M[l] = acc;
-    }
-    __syncthreads();
-  }
-  // this thread's element of A M (A n x k, M k x k)
-  __device__ __forceinline__ double rowmul(const lf* A, const lf* M) {
-    double acc = 0.0;
-    if (act)
-      for (int c = 0; c < k; ++c) acc = acc + A[li * k + c] * M[c * k + lj];
-    return acc;
-  }
   // OUT = P_Xp(U) = U - Xp (Xp^T U); OUT may be U.  Xp, U visible; OUT visible on return
   __device__ __forceinline__ void proj_to(lf* OUT, const lf* Xp, const lf* U) {
     xtu(M1, Xp, U);
@@ -451,57 +406,14 @@ struct Eng {
   }
 
   // ---- Exact_RepMat, RIPTRM.py:433-444 and :599-617, in the pinned frame ---------------------------
-  // The frame (rosenbrock.basisfun; the arithmetic of riptrm_grassmann_so.hip::qr_frame): Householder QR
-  // X = Q [R; 0], vector a k + b = Q e_{k+a} e_b^T; the coordinates of a horizontal U are rows k.. of
-  // Q^T U, coordinate c = element k k + c of the row-major layout.  X visible
-  __device__ __forceinline__ void qr_frame() {
-    W1[l] = act ? X[l] : 0.0;
-    REF[l] = 0.0;
-    __syncthreads();
-    for (int j = 0; j < k; ++j) {
-      const double w = W1[l];
-      const double nrm = sqrt(bsum((act && lj == j && li >= j) ? w * w : 0.0));
-      const double xjj = W1[j * k + j];
-      const double ah = xjj >= 0.0 ? -nrm : nrm;
-      const double beta = nrm > 0.0 ? 1.0 / (nrm * (nrm + fabs(xjj))) : 0.0;   // 2 / (v^T v)
-      __syncthreads();
-      if (act && lj == j && li >= j) REF[l] = (li == j) ? xjj - ah : w;
-      if (l == 0) BETA[j] = beta;
-      __syncthreads();
-      if (l < k) {
-        double acc = 0.0;
-        if (l > j)
-          for (int i = j; i < n; ++i) acc = acc + REF[i * k + j] * W1[i * k + l];
-        CW[l] = acc;
-      }
-      __syncthreads();
-      if (act && lj > j && li >= j) W1[l] = w - (beta * CW[lj]) * REF[li * k + j];
-      __syncthreads();
-    }
-  }
-  // U <- H_j U for reflector j (U n x k, in place).  U visible before and after
-  __device__ __forceinline__ void reflect(lf* U, int j) {
-    if (l < k) {
-      double acc = 0.0;
-      for (int i = j; i < n; ++i) acc = acc + REF[i * k + j] * U[i * k + l];
-      CW[l] = acc;
-    }
-    __syncthreads();
-    if (act && li >= j) U[l] = U[l] - (BETA[j] * CW[lj]) * REF[li * k + j];
-    __syncthreads();
-  }
-  __device__ __forceinline__ void apply_qt(lf* U) {   // U <- Q^T U
-    for (int j = 0; j < k; ++j) reflect(U, j);
-  }
-  __device__ __forceinline__ void apply_q(lf* U) {    // U <- Q U
-    for (int j = k - 1; j >= 0; --j) reflect(U, j);
-  }
+  // The frame is Ops::qr_frame (riptrm_grassmann_ops.h, = rosenbrock.basisfun): coordinate c of a horizontal
+  // U is element k k + c of Q^T U
   // selfadj_operator2matrix (utils.py:565-573) of HwCur at the prepared point (X, Y, S, X^T G_L) in the
   // frame of X: A[i][j] = <b_i, HwCur(b_j)> for i <= j, mirrored -- not the symmetric part; with want_a
   // the coordinates of c too (RIPTRM.py:438-440).  Returns false if an entry is not finite
   __device__ __forceinline__ bool repmat(riptrm_trs::Work& w, bool want_a, double& hvps) {
     const int d = w.dim, lda = w.lda;
-    qr_frame();
+    qr_frame(blk);
     for (int j = 0; j < d; ++j) {
       FV[l] = (l == kk + j) ? 1.0 : 0.0;
       __syncthreads();
@@ -1079,26 +991,15 @@ static GRParams gr_params(riptrm_ctx* c, int mode) {
   return P;
 }
 
-template <int NT>
-static int gr_launch_nt(riptrm_ctx* c, const GRParams& P) {
-  const size_t shm = (size_t)gr_lds_doubles(NT) * sizeof(double);
-  if (P.trail) hipLaunchKernelGGL((k_gr<NT, true>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
-  else hipLaunchKernelGGL((k_gr<NT, false>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
-  HIPCHK(c, hipGetLastError());
-  return RIPTRM_OK;
-}
-
 static int gr_launch(riptrm_ctx* c, const GRParams& P) {
-  switch (gr_threads(P.n * P.k)) {  // the workgroup size is a template parameter (riptrm_trs::Blk)
-    case 64: return gr_launch_nt<64>(c, P);
-    case 128: return gr_launch_nt<128>(c, P);
-    case 192: return gr_launch_nt<192>(c, P);
-    case 256: return gr_launch_nt<256>(c, P);
-    case 320: return gr_launch_nt<320>(c, P);
-    case 384: return gr_launch_nt<384>(c, P);
-    case 448: return gr_launch_nt<448>(c, P);
-    default: return gr_launch_nt<512>(c, P);
-  }
+  return with_nt<gr_threads(NKMAX)>(gr_threads(P.n * P.k), [&](auto nt) -> int {
+    constexpr int NT = decltype(nt)::value;
+    const size_t shm = (size_t)gr_lds_doubles(NT) * sizeof(double);
+    if (P.trail) hipLaunchKernelGGL((k_gr<NT, true>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+    else hipLaunchKernelGGL((k_gr<NT, false>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+    HIPCHK(c, hipGetLastError());
+    return RIPTRM_OK;
+  });
 }
 
 static bool gr_exact_ok(int n, int k) {
@@ -1106,29 +1007,17 @@ static bool gr_exact_ok(int n, int k) {
   return d >= 1 && d <= EXACT_DMAX;
 }
 
-template <int NT>
-static int gr_launch_exact_nt(riptrm_ctx* c, const GRParams& P) {
-  const size_t shm = (size_t)gr_exact_lds_doubles(NT, P.k * (P.n - P.k)) * sizeof(double);
-  const void* fn = P.trail ? (const void*)k_gr_exact<NT, true> : (const void*)k_gr_exact<NT, false>;
-  if (shm > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  if (P.trail) hipLaunchKernelGGL((k_gr_exact<NT, true>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
-  else hipLaunchKernelGGL((k_gr_exact<NT, false>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
-  HIPCHK(c, hipGetLastError());
-  return RIPTRM_OK;
-}
-
-static int gr_launch_exact(riptrm_ctx* c, const GRParams& P) {   // callers checked gr_exact_ok: n k <= 160
-  switch (gr_threads(P.n * P.k)) {
-    case 64: return gr_launch_exact_nt<64>(c, P);
-    case 128: return gr_launch_exact_nt<128>(c, P);
-    default: return gr_launch_exact_nt<EXACT_NT_MAX>(c, P);
-  }
-}
-
-template <int NT>
-static hipError_t gr_occupancy_nt(int* wg) {
-  return hipOccupancyMaxActiveBlocksPerMultiprocessor(wg, (const void*)k_gr<NT, false>, NT,
-                                                      (size_t)gr_lds_doubles(NT) * sizeof(double));
+static int gr_launch_exact(riptrm_ctx* c, const GRParams& P) {   // callers checked gr_exact_ok
+  return with_nt<FRAME_NT_MAX>(gr_threads(P.n * P.k), [&](auto nt) -> int {
+    constexpr int NT = decltype(nt)::value;
+    const size_t shm = (size_t)gr_exact_lds_doubles(NT, P.k * (P.n - P.k)) * sizeof(double);
+    const void* fn = P.trail ? (const void*)k_gr_exact<NT, true> : (const void*)k_gr_exact<NT, false>;
+    if (shm > 64 * 1024) HIPCHK(c, hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    if (P.trail) hipLaunchKernelGGL((k_gr_exact<NT, true>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+    else hipLaunchKernelGGL((k_gr_exact<NT, false>), dim3((unsigned)P.batch), dim3(NT), shm, c->stream, P);
+    HIPCHK(c, hipGetLastError());
+    return RIPTRM_OK;
+  });
 }
 
 extern "C" {
@@ -1312,17 +1201,11 @@ int riptrm_gr_launch_info(riptrm_ctx* ctx, int32_t* lds_bytes, int32_t* threads,
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const int nt = gr_threads(ctx->gr->prob.n * ctx->gr->prob.k);
   int wg = 0;
-  hipError_t e;
-  switch (nt) {
-    case 64: e = gr_occupancy_nt<64>(&wg); break;
-    case 128: e = gr_occupancy_nt<128>(&wg); break;
-    case 192: e = gr_occupancy_nt<192>(&wg); break;
-    case 256: e = gr_occupancy_nt<256>(&wg); break;
-    case 320: e = gr_occupancy_nt<320>(&wg); break;
-    case 384: e = gr_occupancy_nt<384>(&wg); break;
-    case 448: e = gr_occupancy_nt<448>(&wg); break;
-    default: e = gr_occupancy_nt<512>(&wg); break;
-  }
+  const hipError_t e = with_nt<gr_threads(NKMAX)>(nt, [&](auto t) {
+    constexpr int NT = decltype(t)::value;
+    return hipOccupancyMaxActiveBlocksPerMultiprocessor(&wg, (const void*)k_gr<NT, false>, NT,
+                                                        (size_t)gr_lds_doubles(NT) * sizeof(double));
+  });
   HIPCHK(ctx, e);
   *lds_bytes = (int32_t)(gr_lds_doubles(nt) * sizeof(double));
   *threads = nt;

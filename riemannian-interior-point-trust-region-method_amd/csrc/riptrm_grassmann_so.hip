@@ -38,18 +38,16 @@
 #include "riptrm_ctx.h"
 #include "riptrm_wave.h"
 #include "riptrm_trs.h"
+#include "riptrm_grassmann_ops.h"
 
 namespace riptrm_gr_so {
 
 #pragma clang fp contract(off)
 
-constexpr int KMAX = RIPTRM_GR_KMAX;
-constexpr int KK = KMAX * KMAX;
+using namespace riptrm_gr_dev;
+
 constexpr int DMAX = riptrm_trs::DIM_MAX;
 constexpr int NVEC = 5;
-constexpr int LDS_LIMIT = 160 * 1024;
-
-typedef riptrm_trs::lds_f64 lf;
 
 struct SOParams {
   int32_t n, k, npoints, ninst, barrier;
@@ -68,29 +66,24 @@ struct SOParams {
   double* out;                // npoints x RIPTRM_GR_SO_NFIELDS
 };
 
-__host__ __device__ constexpr int so_threads(int N) { return (N + 63) / 64 * 64; }
 __host__ __device__ constexpr int so_lds_doubles(int NT, int d) {
   return NVEC * NT + 3 * KK + KMAX + 2 * (NT / 64) + 3 * DMAX + d * riptrm_trs::lda_of(d) + d * d +
          riptrm_trs::ROT_FIELDS * (DMAX / 2 + 1);
 }
 
 template <int NT>
-struct SO {
+struct SO : Ops {
   const SOParams& P;
-  const int l, n, k, N, kk, d, lda;
-  const int li, lj;
-  const bool act;
-  double alpha, lb;
-  lf *X, *V, *W1, *W2, *REF;   // NT doubles each; REF column j = reflector j of X's QR
-  lf *M1, *MG, *CW, *BETA;     // k x k factors, k column dots, k reflector scales
+  const int d, lda;
+  lf *V, *W2;                  // NT doubles each, with Ops' X, W1 and REF
+  lf *M1, *MG;                 // k x k factors
   lf *GC, *UB, *WV;            // DMAX each: scratch / eigenvalues, step-5 reflector scales, a matrix-vector product
   lf *A, *B, *ROT;             // M (d x lda), the kept gradients (column j at B + j d), the Jacobi rotation table
   riptrm_trs::Blk<NT> blk;
 
   __device__ __forceinline__ SO(const SOParams& P_, double* lds)
-      : P(P_), l((int)threadIdx.x), n(P_.n), k(P_.k), N(P_.n * P_.k), kk(P_.k * P_.k), d(P_.k * (P_.n - P_.k)),
-        lda(riptrm_trs::lda_of(P_.k * (P_.n - P_.k))), li((int)threadIdx.x / P_.k), lj((int)threadIdx.x % P_.k),
-        act((int)threadIdx.x < P_.n * P_.k), alpha(0.0), lb(0.0), blk(lds + NVEC * NT + 3 * KK + KMAX) {
+      : Ops(P_.n, P_.k), P(P_), d(P_.k * (P_.n - P_.k)), lda(riptrm_trs::lda_of(P_.k * (P_.n - P_.k))),
+        blk(lds + NVEC * NT + 3 * KK + KMAX) {
     lf* base = (lf*)lds;
     X = base;  V = base + NT;  W1 = base + 2 * NT;  W2 = base + 3 * NT;  REF = base + 4 * NT;
     lf* f = base + NVEC * NT;
@@ -104,37 +97,7 @@ struct SO {
 
   __device__ __forceinline__ double bsum(double v) { return blk.sum(v); }
 
-  // ---- the pieces of k_gr's HwCur (riptrm_grassmann.hip), same arithmetic --------------------------
-  __device__ __forceinline__ double Tu(const lf* U) {
-    if (!act) return 0.0;
-    const double u = U[l];
-    double acc = 0.0;
-    if (l < N - 1) {
-      const double dd = U[l + 1] - u;
-      acc = -2.0 * alpha * dd + 2.0 * u;
-    }
-    if (l > 0) {
-      const double dm = u - U[l - 1];
-      acc = acc + 2.0 * alpha * dm;
-    }
-    return acc;
-  }
-  // M = A_^T B_ (k x k), one thread per entry, rows in order.  A_, B_ visible; M visible on return
-  __device__ __forceinline__ void xtu(lf* M, const lf* A_, const lf* B_) {
-    if (l < kk) {
-      const int a = l / k, c = l % k;
-      double acc = 0.0;
-      for (int i = 0; i < n; ++i) acc = acc + A_[i * k + a] * B_[i * k + c];
-      M[l] = acc;
-    }
-    __syncthreads();
-  }
-  __device__ __forceinline__ double rowmul(const lf* A_, const lf* M) {
-    double acc = 0.0;
-    if (act)
-      for (int c = 0; c < k; ++c) acc = acc + A_[li * k + c] * M[c * k + lj];
-    return acc;
-  }
+  // ---- H_s from the pieces of k_gr's HwCur (Ops::Tu, xtu, rowmul) ------------------------------------
   // W2 = H_s(V) at (X, y, s); y, s = this thread's multiplier and slack.  V visible; W2 visible on return
   __device__ __forceinline__ void hs(double y, double s) {
     double pv = 0.0;
@@ -151,50 +114,6 @@ struct SO {
     __syncthreads();
     W2[l] = v;
     __syncthreads();
-  }
-
-  // ---- step 1: the reflectors of X = Q [R; 0] into REF / BETA.  X visible ---------------------------
-  __device__ __forceinline__ void qr_frame() {
-    W1[l] = act ? X[l] : 0.0;
-    REF[l] = 0.0;
-    __syncthreads();
-    for (int j = 0; j < k; ++j) {
-      const double w = W1[l];
-      const double nrm = sqrt(bsum((act && lj == j && li >= j) ? w * w : 0.0));
-      const double xjj = W1[j * k + j];
-      const double ah = xjj >= 0.0 ? -nrm : nrm;
-      const double beta = nrm > 0.0 ? 1.0 / (nrm * (nrm + fabs(xjj))) : 0.0;   // 2 / (v^T v)
-      __syncthreads();
-      if (act && lj == j && li >= j) REF[l] = (li == j) ? xjj - ah : w;
-      if (l == 0) BETA[j] = beta;
-      __syncthreads();
-      if (l < k) {
-        double acc = 0.0;
-        if (l > j)
-          for (int i = j; i < n; ++i) acc = acc + REF[i * k + j] * W1[i * k + l];
-        CW[l] = acc;
-      }
-      __syncthreads();
-      if (act && lj > j && li >= j) W1[l] = w - (beta * CW[lj]) * REF[li * k + j];
-      __syncthreads();
-    }
-  }
-  // U <- H_j U for reflector j (U n x k, in place).  U visible before and after
-  __device__ __forceinline__ void reflect(lf* U, int j) {
-    if (l < k) {
-      double acc = 0.0;
-      for (int i = j; i < n; ++i) acc = acc + REF[i * k + j] * U[i * k + l];
-      CW[l] = acc;
-    }
-    __syncthreads();
-    if (act && li >= j) U[l] = U[l] - (BETA[j] * CW[lj]) * REF[li * k + j];
-    __syncthreads();
-  }
-  __device__ __forceinline__ void apply_qt(lf* U) {   // U <- Q^T U
-    for (int j = 0; j < k; ++j) reflect(U, j);
-  }
-  __device__ __forceinline__ void apply_q(lf* U) {    // U <- Q U
-    for (int j = k - 1; j >= 0; --j) reflect(U, j);
   }
 
   __device__ __forceinline__ void write_out(int p, double mineig, double maxeig, double cond, double nulldim,
@@ -233,13 +152,13 @@ struct SO {
     V[l] = 0.0;
     __syncthreads();
     // sym(X^T G_L)
-    const double ef = Tu(X) - ((act && l < N - 1) ? 2.0 : 0.0);
+    const double ef = egrad_f(X);
     W1[l] = act ? ef - y : 0.0;
     __syncthreads();
     xtu(M1, X, W1);
     if (l < kk) MG[l] = 0.5 * (M1[l] + M1[(l % k) * k + l / k]);
     __syncthreads();
-    qr_frame();
+    qr_frame(blk);   // step 1
     // ---- step 2: M, one operator application per column --------------------------------------------
     for (int c = 0; c < d; ++c) {
       V[l] = (l == kk + c) ? 1.0 : 0.0;
@@ -401,15 +320,6 @@ __global__ void __launch_bounds__(NT) k_gr_so(SOParams P) {
   e.run(p);
 }
 
-template <int NT>
-static int so_launch_nt(riptrm_ctx* c, const SOParams& P, size_t shm) {
-  if (shm > 64 * 1024)
-    HIPCHK(c, hipFuncSetAttribute((const void*)k_gr_so<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  hipLaunchKernelGGL(k_gr_so<NT>, dim3((unsigned)P.npoints), dim3(NT), shm, c->stream, P);
-  HIPCHK(c, hipGetLastError());
-  return RIPTRM_OK;
-}
-
 }  // namespace riptrm_gr_so
 
 using namespace riptrm_gr_so;
@@ -434,9 +344,9 @@ int riptrm_gr_second_order(riptrm_ctx* ctx, const double* x, const double* y, in
   if (!inst && npoints > batch)
     return fail(ctx, RIPTRM_E_ARG, "gr_second_order: more points than bound instances need an instance map");
   if (npoints == 0) return RIPTRM_OK;
-  const int nt = so_threads(N);
+  const int nt = gr_threads(N);
   const size_t shm = (size_t)so_lds_doubles(nt, d) * sizeof(double);
-  if (nt > 192 || shm > (size_t)LDS_LIMIT)
+  if (nt > FRAME_NT_MAX || shm > (size_t)LDS_LIMIT)
     return fail(ctx, RIPTRM_E_ARG, "gr_second_order: the shape does not fit one workgroup's LDS");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   SOParams P;
@@ -459,11 +369,14 @@ int riptrm_gr_second_order(riptrm_ctx* ctx, const double* x, const double* y, in
   P.linindtol = linindtol;
   P.mu = mu;
   P.out = out;
-  switch (nt) {
-    case 64: return so_launch_nt<64>(ctx, P, shm);
-    case 128: return so_launch_nt<128>(ctx, P, shm);
-    default: return so_launch_nt<192>(ctx, P, shm);
-  }
+  return with_nt<FRAME_NT_MAX>(nt, [&](auto t) -> int {
+    constexpr int NT = decltype(t)::value;
+    if (shm > 64 * 1024)
+      HIPCHK(ctx, hipFuncSetAttribute((const void*)k_gr_so<NT>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
+    hipLaunchKernelGGL(k_gr_so<NT>, dim3((unsigned)P.npoints), dim3(NT), shm, ctx->stream, P);
+    HIPCHK(ctx, hipGetLastError());
+    return RIPTRM_OK;
+  });
 }
 
 }  // extern "C"

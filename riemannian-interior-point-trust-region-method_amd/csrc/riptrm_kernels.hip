@@ -98,14 +98,6 @@ __device__ __forceinline__ void bsum(Red& R, double (&v)[K]) {
   bred<K>(R, v, op);
 }
 
-// numpy.minimum / numpy.maximum (NaN-propagating) used by the dual clipping (RIPTRM.py:681-683)
-__device__ __forceinline__ double np_min(double a, double b) {
-  return (isnan(a) || isnan(b)) ? NAN : (b < a ? b : a);
-}
-__device__ __forceinline__ double np_max(double a, double b) {
-  return (isnan(a) || isnan(b)) ? NAN : (b > a ? b : a);
-}
-
 // ------------------------------------------------------------------------------------------
 // k_gemv: batched fp64 mat-vec over the active instances.  Workgroup = GV_RB rows of one
 // instance; each wave owns GV_RW rows and streams them in 1 KiB (64 lanes x 16 B) column

@@ -35,6 +35,10 @@ namespace riptrm_si {
 
 #pragma clang fp contract(off)
 
+using riptrm::np_max;
+using riptrm::np_min;
+using riptrm::round_up;
+
 constexpr int W = 64;
 constexpr int DMAX = RIPTRM_SI_DMAX;
 constexpr int MMAX = RIPTRM_SI_MMAX;
@@ -93,8 +97,6 @@ struct Layout {
   int64_t off_tW;              // k_si_prep's per-lane records
 };
 
-inline int64_t rup(int64_t a, int64_t m) { return (a + m - 1) / m * m; }
-
 // manifold.dim of Product(Skew(d), SPD(d), SPD(d)) and whether its Exact_RepMat subproblem takes the
 // HBM path (parked instances served by the host's batched TRS service, riptrm_trs_big.hip)
 __host__ __device__ constexpr int si_manifold_dim(int d) { return d * (d - 1) / 2 + d * (d + 1); }
@@ -117,43 +119,39 @@ inline Layout make_layout(int d, int N, int m, int batch, int cap) {
   Layout L;
   const int64_t v3 = 3LL * d * d;
   int64_t o = 0;
-  L.off_x = o;     o = rup(o + 8 * batch * v3, 256);
-  L.off_y = o;     o = rup(o + 8LL * batch * m, 256);
-  L.off_eta = o;   o = rup(o + 8 * batch * v3, 256);
-  L.off_heta = o;  o = rup(o + 8 * batch * v3, 256);
-  L.off_escr = o;  o = rup(o + 8LL * batch * d * N, 256);
-  L.off_stats = o; o = rup(o + 8LL * batch * RIPTRM_STAT_NFIELDS, 256);
-  L.off_log = o;   o = rup(o + 8LL * batch * cap * RIPTRM_LOG_NFIELDS, 256);
+  L.off_x = o;     o = round_up(o + 8 * batch * v3, 256);
+  L.off_y = o;     o = round_up(o + 8LL * batch * m, 256);
+  L.off_eta = o;   o = round_up(o + 8 * batch * v3, 256);
+  L.off_heta = o;  o = round_up(o + 8 * batch * v3, 256);
+  L.off_escr = o;  o = round_up(o + 8LL * batch * d * N, 256);
+  L.off_stats = o; o = round_up(o + 8LL * batch * RIPTRM_STAT_NFIELDS, 256);
+  L.off_log = o;   o = round_up(o + 8LL * batch * cap * RIPTRM_LOG_NFIELDS, 256);
   L.off_tA = L.off_tP = L.off_tids = L.off_tE = L.off_ta = L.off_tx = L.off_tD = L.off_tlam = L.off_tkind = L.off_tmin = L.off_rs = 0;
   L.off_tC = L.tC_stride = L.off_tW = 0;
   if (si_hbm_trs(d)) {
     const int64_t td = si_manifold_dim(d), tp = si_tdp(d);
-    L.off_tA = o;    o = rup(o + 8 * batch * td * td, 256);
-    L.off_tP = o;    o = rup(o + 8LL * batch * (3LL * d * d + m + 1), 256);
-    L.off_tids = o;  o = rup(o + 4LL * 2 * batch, 256);
+    L.off_tA = o;    o = round_up(o + 8 * batch * td * td, 256);
+    L.off_tP = o;    o = round_up(o + 8LL * batch * (3LL * d * d + m + 1), 256);
+    L.off_tids = o;  o = round_up(o + 4LL * 2 * batch, 256);
     if (!si_repmat_e_lds(d, N)) {
-      L.off_tE = o;  o = rup(o + 8 * batch * td * d * N, 256);
+      L.off_tE = o;  o = round_up(o + 8 * batch * td * d * N, 256);
     }
-    L.off_ta = o;    o = rup(o + 8 * batch * tp, 256);
-    L.off_tx = o;    o = rup(o + 8 * batch * tp, 256);
-    L.off_tD = o;    o = rup(o + 8LL * batch, 256);
-    L.off_tlam = o;  o = rup(o + 8LL * batch, 256);
-    L.off_tkind = o; o = rup(o + 4LL * batch, 256);
-    L.off_tmin = o;  o = rup(o + 8LL * batch, 256);
-    L.off_rs = o;    o = rup(o + 8 * batch * si_rs_doubles(d), 256);
-    L.off_tW = o;    o = rup(o + 8LL * batch * SI_PREP_F * si_nt(d), 256);
+    L.off_ta = o;    o = round_up(o + 8 * batch * tp, 256);
+    L.off_tx = o;    o = round_up(o + 8 * batch * tp, 256);
+    L.off_tD = o;    o = round_up(o + 8LL * batch, 256);
+    L.off_tlam = o;  o = round_up(o + 8LL * batch, 256);
+    L.off_tkind = o; o = round_up(o + 4LL * batch, 256);
+    L.off_tmin = o;  o = round_up(o + 8LL * batch, 256);
+    L.off_rs = o;    o = round_up(o + 8 * batch * si_rs_doubles(d), 256);
+    L.off_tW = o;    o = round_up(o + 8LL * batch * SI_PREP_F * si_nt(d), 256);
     if (td <= RIPTRM_EIG_COMPACT_MAX) {   // keyed by the park point (x, y, mu): 3dd + m + 1 doubles
-      L.tC_stride = rup(riptrm_big_kcache_doubles((int)td, 3 * d * d + m + 1), 32);
-      L.off_tC = o;  o = rup(o + 8 * batch * L.tC_stride, 256);
+      L.tC_stride = round_up(riptrm_big_kcache_doubles((int)td, 3 * d * d + m + 1), 32);
+      L.off_tC = o;  o = round_up(o + 8 * batch * L.tC_stride, 256);
     }
   }
   L.total = o;
   return L;
 }
-
-// numpy.minimum / numpy.maximum (NaN-propagating), RIPTRM.py:681-683
-__device__ __forceinline__ double np_min(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b < a ? b : a); }
-__device__ __forceinline__ double np_max(double a, double b) { return (isnan(a) || isnan(b)) ? NAN : (b > a ? b : a); }
 
 // value of v on lane src.  A wave op: call it on every lane (never inside a lane-dependent
 // branch or ?:), inactive source lanes read as 0.

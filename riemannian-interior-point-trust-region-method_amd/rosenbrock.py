@@ -146,6 +146,16 @@ def second_order_columns(so: Dict[str, np.ndarray]) -> Dict[str, list]:
             "condition_number": [None if np.isnan(v) else np.float64(v) for v in so["cond"]]}
 
 
+def _hessian_f(alpha, u):
+    """T u for an n x k array u: the constant tridiagonal Euclidean Hessian of f on the row-major flattening."""
+    w = u.ravel()
+    dd = w[1:] - w[:-1]
+    acc = np.zeros(w.size)
+    acc[:-1] = -2.0 * alpha * dd + 2.0 * w[:-1]
+    acc[1:] += 2.0 * alpha * dd
+    return acc.reshape(u.shape)
+
+
 def symmetric_second_order(n, k, alpha, lb, x, y, active_tol=ACTIVE_TOL):
     """(mineig, cond or None) of the symmetric-part operator H_s(V) = P_X(T V) - V sym(X^T G_L) on the
     horizontal directions orthogonal to the active gradients, in numpy on the host.  Only the callback
@@ -153,14 +163,7 @@ def symmetric_second_order(n, k, alpha, lb, x, y, active_tol=ACTIVE_TOL):
     x = np.asarray(x, dtype=np.float64).reshape(n, k)
     N = n * k
 
-    def Tu(u):
-        w = u.ravel()
-        dd = w[1:] - w[:-1]
-        acc = np.zeros(N)
-        acc[:-1] = -2.0 * alpha * dd + 2.0 * w[:-1]
-        acc[1:] += 2.0 * alpha * dd
-        return acc.reshape(n, k)
-
+    Tu = lambda u: _hessian_f(alpha, u)
     two = np.full(N, 2.0)
     two[-1] = 0.0
     GL = Tu(x) - two.reshape(n, k) - np.asarray(y, dtype=np.float64).reshape(n, k)
@@ -221,14 +224,7 @@ class _CallbackProbeProblem:
         two = np.full(N, 2.0)
         two[-1] = 0.0
 
-        def Tu(u):
-            w = u.ravel()
-            dd = w[1:] - w[:-1]
-            acc = np.zeros(N)
-            acc[:-1] = -2.0 * alpha * dd + 2.0 * w[:-1]
-            acc[1:] += 2.0 * alpha * dd
-            return acc.reshape(n, k)
-
+        Tu = lambda u: _hessian_f(alpha, u)
         egrad = lambda x: Tu(x) - two.reshape(n, k)
         self.riemannian_hessian = lambda x, v: M.projection(x, Tu(v)) - v @ (x.T @ egrad(x))
         unit = lambda i: -np.eye(N)[i].reshape(n, k)
@@ -302,10 +298,10 @@ def rosenbrock_callback_kind(f) -> int:
 
 def householder_complement(x):
     """Columns k.. of Q in the Householder QR X = Q [R; 0] (n x (n - k)), with the arithmetic and the sign
-    convention of ``csrc/riptrm_grassmann_so.hip::qr_frame``: reflector j is H_j = I - beta_j v_j v_j^T with
-    v_j = w - ahat e_j, w = column j of H_{j-1} .. H_0 X from row j down, ahat = -||w|| if w_j >= 0 else
-    +||w|| (LAPACK dlarfg's sign: R gets a non-positive diagonal wherever w_j >= 0), beta_j =
-    1 / (||w|| (||w|| + |w_j|)), and Q = H_0 H_1 .. H_{k-1}."""
+    convention of ``csrc/riptrm_grassmann_ops.h::qr_frame`` (the one frame of k_gr_exact and k_gr_so):
+    reflector j is H_j = I - beta_j v_j v_j^T with v_j = w - ahat e_j, w = column j of H_{j-1} .. H_0 X from
+    row j down, ahat = -||w|| if w_j >= 0 else +||w|| (LAPACK dlarfg's sign: R gets a non-positive diagonal
+    wherever w_j >= 0), beta_j = 1 / (||w|| (||w|| + |w_j|)), and Q = H_0 H_1 .. H_{k-1}."""
     x = np.asarray(x, dtype=np.float64)
     n, k = x.shape
     W = x.copy()

@@ -27,6 +27,9 @@ sqrt(k) / 8).  Where the device flips there -- measured: row 1 at (13, 5) and (1
 the rows before the tie row by row and the run after it at the outer level only (same outer iterations and end
 states, residuals within 1e-3 or 10 mu); the tie row itself has the same input on both sides, so its dxtype is
 asserted too, and the row values at those shapes are what the teacher-forced test checks.
+
+One frame: at k = 1 the smallest eigenvalue of this kernel's matrix and of the second-order kernel's (barrier term
+on, no active constraint) agree within one bar per kernel (test_exact_and_second_order_kernels_share_one_frame).
 """
 import ctypes
 
@@ -374,3 +377,33 @@ def test_nonfinite_instance_stops_alone():
         for b in (0, 2, 3):
             assert np.array_equal(_bits(np.asarray(out[key][b], dtype=np.float64)),
                                   _bits(np.asarray(clean[key][b], dtype=np.float64))), (key, b)
+
+
+@pytest.mark.parametrize("n,k", [(4, 1), (7, 1)])
+def test_exact_and_second_order_kernels_share_one_frame(n, k):
+    """k_gr_exact and k_gr_so take the frame from one definition (csrc/riptrm_grassmann_ops.h).  With k = 1,
+    X^T G_L is a number and HwCur is self-adjoint, so the mirrored upper triangle (exact_step) and the symmetrised
+    matrix (second_order with barrier=True) are one matrix up to rounding, and with no active constraint their
+    smallest eigenvalues agree.  Bar: each kernel is held to bar_of (32 d eps scale) against its own CPU statement,
+    so the two differ by 2 bar_of at most; on the CPU, in the basisfun frame, the two statements differ by at most
+    0.013 of one such bar.  Measured on the MI355X: worst 0.0022 of the 2 bar_of bar at (4, 1), 0.0012 at (7, 1)."""
+    import rosenbrock_second_order as S
+    rs = np.random.RandomState(100 * n + k)
+    alphas = np.repeat(S.ALPHAS, 4)
+    B = len(alphas)
+    xs = np.stack([R.feasible_point(n, k, rs) for _ in range(B)])
+    ys = 0.1 + rs.rand(B, n * k)
+    mus = np.full(B, S.MU)
+    eng = _engine(n, k, B, alphas)
+    ex = eng.exact_step(xs, ys, mus, np.full(B, 0.1))
+    so = eng.second_order(xs, ys, barrier=True, mu=mus)
+    worst = 0.0
+    for b in range(B):
+        bar = 2 * S.bar_of(R.RosenbrockStructured(n, k, alphas[b]), xs[b], ys[b], barrier=True)
+        err = abs(ex["mineig"][b] - so["mineig"][b])
+        worst = max(worst, err / bar)
+        print(f"({n}, {k}) alpha={alphas[b]:g}: exact {ex['mineig'][b]:.17g}, second order {so['mineig'][b]:.17g}, "
+              f"difference {err:.3g} = {err / bar:.3g} of the bar {bar:.3g}")
+        assert so["info"][b] == 0 and so["nactive"][b] == 0, (b, so["nactive"][b])
+        assert err <= bar, (b, err, bar)
+    print(f"({n}, {k}): worst difference {worst:.3g} of 2 bar_of")
