@@ -91,6 +91,13 @@ class RIPTRM(Solver):
 
     SI_LOG_BYTES = 8e9   # upper bound of the StableIdentification device log per batch
 
+    @classmethod
+    def one_launch_log_capacity(cls, batch: int, log_capacity: int | None = None, row_bytes: int = 256) -> int:
+        """Log rows per instance of a one-launch engine: the requested ones (default 65536), capped so `batch`
+        instances at `row_bytes` per row stay within SI_LOG_BYTES, and at least 16."""
+        req = 65536 if log_capacity is None else int(log_capacity)
+        return max(16, min(req, int(cls.SI_LOG_BYTES // (row_bytes * batch))))
+
     def run_batch(self, problems: Sequence[Any], log_capacity: int | None = None) -> List[Output]:
         """NonnegPCA: the device log is drained to the host whenever it is half full, so logs of
         any length are complete (log_capacity = rows of the device ring, default 8192).
@@ -104,13 +111,9 @@ class RIPTRM(Solver):
             raise NotImplementedError("callbackfun cannot run on the device (only the Rosenbrock simulator's "
                                       "second-order residual does, on Rosenbrock problems)")
         if all(isinstance(p, SIProblem) for p in problems):
-            req = 65536 if log_capacity is None else int(log_capacity)
-            cap = max(16, min(req, int(self.SI_LOG_BYTES // (256 * len(problems)))))
-            return self._run_batch_si(problems, cap)
+            return self._run_batch_si(problems, self.one_launch_log_capacity(len(problems), log_capacity))
         if all(isinstance(p, RosenbrockProblem) for p in problems):
-            req = 65536 if log_capacity is None else int(log_capacity)
-            cap = max(16, min(req, int(self.SI_LOG_BYTES // (256 * len(problems)))))
-            return self._run_batch_rosenbrock(problems, cap)
+            return self._run_batch_rosenbrock(problems, self.one_launch_log_capacity(len(problems), log_capacity))
         if log_capacity is None:
             log_capacity = 8192
         for p in problems:
@@ -133,11 +136,16 @@ class RIPTRM(Solver):
         self.last_layout = eng.layout_name
         x0 = np.stack([np.asarray(p.initialpoint, dtype=np.float64) for p in problems])
         y0 = np.stack([np.asarray(p.initialineqLagmult, dtype=np.float64) for p in problems])
+        return self._solve(eng, x0, y0, log_capacity, lambda x: x.copy())
+
+    def _solve(self, eng, x0, y0, log_capacity, point) -> List[Output]:
+        """The shared tail of run_batch: solve on the engine, keep the result (last_batch) and build the
+        Outputs; `point` makes an Output's x of one instance's row of the final points."""
         res = eng.solve(x0, y0, self.option)
         self.last_batch = res
         xs = res.x.cpu().numpy()
         ys = res.y.cpu().numpy()
-        return self._outputs(res, [xs[b].copy() for b in range(B)], ys, log_capacity)
+        return self._outputs(res, [point(x) for x in xs], ys, log_capacity)
 
     def _run_batch_si(self, problems: List[SIProblem], log_capacity: int) -> List[Output]:
         """StableIdentification (src/StableIdentification/coordinator.py): one workgroup per
@@ -173,12 +181,7 @@ class RIPTRM(Solver):
         self.last_layout = "si-shared" if same else "si"
         x0 = np.stack([p.point_array() for p in problems])
         y0 = np.stack([np.asarray(p.initialineqLagmult, dtype=np.float64) for p in problems])
-        res = eng.solve(x0, y0, self.option)
-        self.last_batch = res
-        xs = res.x.cpu().numpy()
-        ys = res.y.cpu().numpy()
-        return self._outputs(res, [[xs[b, 0].copy(), xs[b, 1].copy(), xs[b, 2].copy()] for b in range(B)], ys,
-                             log_capacity)
+        return self._solve(eng, x0, y0, log_capacity, lambda x: [x[0].copy(), x[1].copy(), x[2].copy()])
 
     def _run_batch_rosenbrock(self, problems: List[RosenbrockProblem], log_capacity: int) -> List[Output]:
         """Rosenbrock on Grassmann(n, k) (src/Rosenbrock/coordinator.py): one workgroup per problem,
@@ -198,18 +201,14 @@ class RIPTRM(Solver):
                 raise NotImplementedError(f"callbackfun: the second-order residual needs manifold dimension k (n - k) "
                                           f"<= {C['RIPTRM_TRS_DIM_MAX']} (got {k * (n - k)} at n = {n}, k = {k})")
             # the trail keeps 2 n k doubles per log row: log + trail stay within SI_LOG_BYTES
-            log_capacity = max(16, min(log_capacity, int(self.SI_LOG_BYTES // ((256 + 16 * n * k) * B))))
+            log_capacity = self.one_launch_log_capacity(B, log_capacity, 256 + 16 * n * k)
         eng = RosenbrockBatch(n, k, B, log_capacity=log_capacity)
         eng.load(np.array([p.alpha for p in problems]), np.array([p.lb for p in problems]))
         self.last_layout = "rosenbrock"
         self.last_engine = eng   # with a callback: its trail holds the point of every log row
         x0 = np.stack([np.asarray(p.initialpoint, dtype=np.float64) for p in problems])
         y0 = np.stack([np.asarray(p.initialineqLagmult, dtype=np.float64) for p in problems])
-        res = eng.solve(x0, y0, self.option)
-        self.last_batch = res
-        xs = res.x.cpu().numpy()
-        ys = res.y.cpu().numpy()
-        return self._outputs(res, [xs[b].copy() for b in range(B)], ys, log_capacity)
+        return self._solve(eng, x0, y0, log_capacity, lambda x: x.copy())
 
     def _outputs(self, res, xs, ys, log_capacity) -> List[Output]:
         outs = []

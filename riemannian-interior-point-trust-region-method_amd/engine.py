@@ -220,6 +220,32 @@ def _stream_handle(device: torch.device) -> int:
     return torch.cuda.current_stream(device).cuda_stream
 
 
+def ptr(t: Optional[torch.Tensor]) -> Optional[ctypes.c_void_p]:
+    """A tensor's first element as the void pointer of a C-ABI call (None stays None)."""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
+
+
+def align256(buf: torch.Tensor):
+    """(first 256-aligned address inside `buf`, bytes of `buf` from there on)."""
+    base = buf.data_ptr()
+    pad = (-base) % 256
+    return base + pad, buf.numel() * buf.element_size() - pad
+
+
+def aligned_buffer(nbytes: int, device, zero: bool = False):
+    """`nbytes` of memory on `device` from a 256-aligned address: (the uint8 tensor that owns it, allocated
+    with 256 bytes of slack; the aligned address; the bytes usable from there, >= nbytes)."""
+    buf = (torch.zeros if zero else torch.empty)(int(nbytes) + 256, dtype=torch.uint8, device=device)
+    return (buf, *align256(buf))
+
+
+def host_array(a, shape) -> np.ndarray:
+    """`a` as a writable float64 array of `shape` that owns its data: reshaped when the element counts
+    agree, broadcast otherwise (a scalar or one row for the whole batch)."""
+    a = np.asarray(a, dtype=np.float64)
+    return np.array(a.reshape(shape) if a.size == math.prod(shape) else np.broadcast_to(a, shape), order="C")
+
+
 EXACT_BIG_CHUNK = 4        # lock-step iterations per advance on the HBM Exact_RepMat path
 TRS_WS_BUDGET = 16 << 30   # bytes of HBM the Exact_RepMat scratch may take (RIPTRM_TRS_WS_GB overrides)
 
@@ -239,12 +265,10 @@ def bind_trs_scratch(ctx, lib, device, have, order: int, slots: int):
     to keep."""
     if have is None or have[1] < order or have[2] < slots:
         nbytes = int(lib.riptrm_trs_workspace_bytes(int(order), int(slots)))
-        have = (torch.empty(nbytes + 256, dtype=torch.uint8, device=device), int(order), int(slots))
-    buf = have[0]
-    base = buf.data_ptr()
-    ptr = base + (-base) % 256
-    ctx.check(lib.riptrm_trs_bind_workspace(ctx.h, ctypes.c_void_p(ptr), buf.numel() - (ptr - base), int(order),
-                                            int(slots)), "riptrm_trs_bind_workspace")
+        have = (aligned_buffer(nbytes, device)[0], int(order), int(slots))
+    addr, usable = align256(have[0])
+    ctx.check(lib.riptrm_trs_bind_workspace(ctx.h, ctypes.c_void_p(addr), usable, int(order), int(slots)),
+              "riptrm_trs_bind_workspace")
     return have
 
 
@@ -274,7 +298,157 @@ def trs_cache_wanted(lib, order: int, batch: int) -> int:
 LAYOUTS = {"full": C["RIPTRM_LAYOUT_FULL"], "sym": C["RIPTRM_LAYOUT_SYMTILE"], "shared": C["RIPTRM_LAYOUT_SHARED"]}
 
 
-class NonnegPCABatch:
+class DeviceBatch:
+    """What the batch engines of every problem share on the host: the library and its context, the
+    256-aligned workspace PyTorch owns, typed views into it (kinds 0..3 = x, y, eta, Heta, 4 = stats,
+    5 = log slots; riptrm_workspace_offset and its per-problem twins), host-to-device staging and the
+    Exact_RepMat counters.  A subclass sets its dimensions, hands its byte count to ``_allocate`` and
+    answers ``_offset``."""
+
+    def __init__(self, batch: int, log_capacity: int, device: Optional[int] = None):
+        if not torch.cuda.is_available():
+            raise RuntimeError(f"{type(self).__name__} needs a ROCm GPU (gfx950); there is no CPU fallback")
+        self.lib = N.load()
+        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
+        self.batch, self.cap = int(batch), int(log_capacity)
+        self._keep: List[torch.Tensor] = []   # what the running solve reads: kept alive until the next begin()
+        self.ro: Optional[ResolvedOptions] = None
+
+    def _allocate(self, nbytes: int):
+        """The context and the zeroed workspace of `nbytes`, once the subclass knows its dimensions."""
+        self.ctx = N.Context(self.device.index, _stream_handle(self.device))
+        self.ws, self.ws_ptr, _ = aligned_buffer(nbytes, self.device, zero=True)
+        self._pad = self.ws_ptr - self.ws.data_ptr()
+        self.ws_bytes = int(nbytes)
+
+    def _offset(self, kind: int) -> int:
+        raise NotImplementedError
+
+    def _sync_stream(self):
+        self.ctx.set_stream(_stream_handle(self.device))
+
+    # ---- views into the workspace -------------------------------------------------------
+    def _view(self, kind: int, shape, dtype=torch.float64):
+        count = int(np.prod(shape))
+        start = self._pad + int(self._offset(kind))
+        return self.ws[start:start + count * 8].view(dtype).view(*shape)
+
+    def stats(self) -> np.ndarray:
+        return self._view(4, (self.batch, NSTAT)).cpu().numpy().copy()
+
+    def log_rows(self, count: int) -> np.ndarray:
+        lg = self._view(5, (self.batch, self.cap, NLOG))
+        return lg[:, :max(0, min(count, self.cap))].cpu().numpy()
+
+    def _dev(self, a, shape) -> torch.Tensor:
+        """`a` on the device as a contiguous float64 tensor of `shape`: a float64 tensor already there is
+        reshaped without a copy, anything else goes through ``host_array``."""
+        if isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64:
+            return a.reshape(shape).contiguous()
+        return torch.as_tensor(host_array(a, shape)).to(self.device).contiguous()
+
+    # ---- Exact_RepMat counters ----------------------------------------------------------
+    def trs_skip_stats(self):
+        """(Exact_RepMat subproblems whose CG went through the certified skip test, CGs skipped) since
+        the context was created (riptrm_trs_skip_stats; the tridiagonal path from order 150 on counts
+        here, the eigen-coordinate path below does not)."""
+        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.check(self.lib.riptrm_trs_skip_stats(self.ctx.h, ctypes.byref(a), ctypes.byref(b)), "riptrm_trs_skip_stats")
+        return int(a.value), int(b.value)
+
+    def trs_cache_stats(self):
+        """(subproblems served from the keyed eigendecomposition cache, subproblems served) of the
+        last solve on the HBM Exact_RepMat path (riptrm_trs_cache_stats)."""
+        h, t = ctypes.c_int64(0), ctypes.c_int64(0)
+        self.ctx.check(self.lib.riptrm_trs_cache_stats(self.ctx.h, ctypes.byref(h), ctypes.byref(t)),
+                       "riptrm_trs_cache_stats")
+        return int(h.value), int(t.value)
+
+
+class OneLaunchBatch(DeviceBatch):
+    """The engines that run every solve of the batch in one launch, one workgroup per instance
+    (StableIdentification, Rosenbrock).  A subclass names its C-ABI family (``abi``: riptrm_<abi>_hvp /
+    _tcg / _solve take the same arguments in both) and sets ``point_shape`` (one instance's point) and
+    ``mult_len`` (its multipliers); its ``begin`` resolves the options and ends in ``_launch``."""
+
+    abi = ""
+
+    def _call(self, entry: str, *args):
+        name = f"riptrm_{self.abi}_{entry}"
+        self.ctx.check(getattr(self.lib, name)(self.ctx.h, *args), name)
+
+    def _pt(self, a) -> torch.Tensor:
+        return self._dev(a, (self.batch, *self.point_shape))
+
+    def _mult(self, a) -> torch.Tensor:
+        return self._dev(a, (self.batch, self.mult_len))
+
+    def _vec(self, a) -> torch.Tensor:
+        return self._dev(a, (self.batch,))
+
+    def x(self):
+        return self._view(0, (self.batch, *self.point_shape))
+
+    def y(self):
+        return self._view(1, (self.batch, self.mult_len))
+
+    def eta(self):
+        return self._view(2, (self.batch, *self.point_shape))
+
+    def heta(self):
+        return self._view(3, (self.batch, *self.point_shape))
+
+    def hvp(self, x, y, mu, v) -> torch.Tensor:
+        """HwCur(v) at (x, y, mu) per instance; x, v: (batch, *point_shape), y: (batch, mult_len), mu: a
+        scalar or one per instance."""
+        X, Y, M, V = self._pt(x), self._mult(y), self._vec(mu), self._pt(v)
+        out = torch.zeros_like(X)
+        self._sync_stream()
+        self._call("hvp", ptr(X), ptr(Y), ptr(M), ptr(V), ptr(out))
+        torch.cuda.synchronize(self.device)
+        return out
+
+    def tcg(self, x, y, mu, Delta):
+        """tCG at (x, y, mu, Delta) per instance: (eta, Heta, j at exit, stop reason)."""
+        X, Y, M, D = self._pt(x), self._mult(y), self._vec(mu), self._vec(Delta)
+        self._sync_stream()
+        self._call("tcg", None, ptr(X), ptr(Y), ptr(M), ptr(D))
+        torch.cuda.synchronize(self.device)
+        st = self.stats()
+        js = st[:, C["RIPTRM_STAT_TCG_LAST_J"]].astype(int)
+        stops = [TCG_NAMES[int(s)] for s in st[:, C["RIPTRM_STAT_TCG_LAST_STOP"]]]
+        return self.eta().clone(), self.heta().clone(), js, stops
+
+    def _launch(self, ro: ResolvedOptions, x0, y0) -> ResolvedOptions:
+        """Start every solve of the batch from (x0, y0) under the resolved options (riptrm_<abi>_solve)."""
+        X, Y = self._pt(x0), self._mult(y0)
+        tabs = ro.device_tables(self.device)
+        self._keep = [X, Y] + tabs
+        self._sync_stream()
+        self._call("solve", ctypes.byref(ro.c_opt), *map(ptr, (X, Y, *tabs[:3])), len(ro.mu_tab))
+        self.ro = ro
+        return ro
+
+    def solve(self, x0, y0, option: Dict[str, Any], restart_every: int = 0) -> "BatchResult":
+        self.begin(x0, y0, option, restart_every)
+        return self.result()
+
+    def result(self) -> "BatchResult":
+        torch.cuda.synchronize(self.device)
+        st = self.stats()
+        count = st[:, C["RIPTRM_STAT_LOG_COUNT"]].astype(np.int64)
+        cap = min(self.cap, int(self.ro.c_opt.log_capacity))
+        slots = self.log_rows(int(count.max()) if self.batch else 0)
+        logs, dropped = [], []
+        for b in range(self.batch):   # one launch per solve: no draining, head + latest records kept
+            rows, drop = assemble_log(slots[b], int(count[b]), cap)
+            logs.append(rows.copy())
+            dropped.append(drop)
+        return BatchResult(x=self.x().clone(), y=self.y().clone(), stats=st, raw_log=logs, ro=self.ro,
+                           dropped=np.array(dropped))
+
+
+class NonnegPCABatch(DeviceBatch):
     """A batch of NonnegPCA instances with a common n, resident on one GPU.
 
     layout "sym" (default) / "full": one S = Z + Z^T per instance.  layout "shared": ONE S for the
@@ -284,13 +458,10 @@ class NonnegPCABatch:
     def __init__(self, n: int, batch: int, device: Optional[int] = None, log_capacity: int = 4096,
                  layout: str = "sym", stream_groups: int = 0, spass_kind: int = 1, drain_logs: bool = True,
                  persistent: int = 1):
-        if not torch.cuda.is_available():
-            raise RuntimeError("NonnegPCABatch needs a ROCm GPU (gfx950); there is no CPU fallback")
+        super().__init__(batch, log_capacity, device)
         if n < 2 or batch < 1:
             raise ValueError("need n >= 2 and batch >= 1")
-        self.lib = N.load()
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self.n, self.batch, self.cap = int(n), int(batch), int(log_capacity)
+        self.n = int(n)
         if layout not in LAYOUTS:
             raise ValueError(f"layout must be one of {sorted(LAYOUTS)}")
         self.layout_name = layout
@@ -299,21 +470,14 @@ class NonnegPCABatch:
         self.rows = int(self.lib.riptrm_nonnegpca_rows(self.n))
         self.shared = layout == "shared"
         self.inst_stride = int(self.lib.riptrm_nonnegpca_s_elems(self.n, self.layout))
-        self.ctx = N.Context(self.device.index, _stream_handle(self.device))
+        self._allocate(int(self.lib.riptrm_workspace_bytes(self.n, self.batch, self.cap, self.layout)))
         self.ctx.check(self.lib.riptrm_set_stream_groups(self.ctx.h, int(stream_groups)), "riptrm_set_stream_groups")
         self.ctx.check(self.lib.riptrm_set_spass_kind(self.ctx.h, int(spass_kind)), "riptrm_set_spass_kind")
         # small symmetric-tile batches: the whole lock-step loop in one launch per chunk (k_persist)
         self.ctx.check(self.lib.riptrm_set_persistent(self.ctx.h, int(persistent)), "riptrm_set_persistent")
         self.S = torch.zeros((1 if self.shared else self.batch, self.inst_stride), dtype=torch.float64,
                              device=self.device)
-        nbytes = int(self.lib.riptrm_workspace_bytes(self.n, self.batch, self.cap, self.layout))
-        self.ws = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-        base = self.ws.data_ptr()
-        self._ws_pad = (-base) % 256
-        self.ws_ptr = base + self._ws_pad
-        self.ws_bytes = nbytes
         self.bound = False
-        self._keep: List[torch.Tensor] = []
         self._trs_ws = None   # (buffer, order, slots) of Exact_RepMat above RIPTRM_TRS_DIM_MAX
         self._trs_cache: Optional[torch.Tensor] = None   # its eigendecomposition cache
         # log records copied to the host by drain_logs() (riptrm_log_rebase), per instance
@@ -322,28 +486,18 @@ class NonnegPCABatch:
         self._dropped = np.zeros(self.batch, dtype=np.int64)
 
     # ---- views into the workspace -------------------------------------------------------
-    def _view(self, kind: int, shape, dtype=torch.float64):
-        off = int(self.lib.riptrm_workspace_offset(self.n, self.batch, self.cap, self.layout, kind))
-        count = int(np.prod(shape))
-        start = self._ws_pad + off
-        return self.ws[start:start + count * 8].view(dtype).view(*shape)
+    def _offset(self, kind: int) -> int:
+        return self.lib.riptrm_workspace_offset(self.n, self.batch, self.cap, self.layout, kind)
 
     def vec(self, kind: int) -> torch.Tensor:
         """kind 0 = x, 1 = y, 2 = eta, 3 = Heta (batch, n) views (no copy)."""
         return self._view(kind, (self.batch, self.ld))[:, :self.n]
 
-    def stats(self) -> np.ndarray:
-        return self._view(4, (self.batch, NSTAT)).cpu().numpy().copy()
-
-    def log_rows(self, count: int) -> np.ndarray:
-        lg = self._view(5, (self.batch, self.cap, NLOG))
-        return lg[:, :max(0, min(count, self.cap))].cpu().numpy()
-
     def _pending_logs(self, st: np.ndarray):
         """Per instance: the records written since the last rebase, in order, and how many of them
         the slots dropped."""
         k = (st[:, C["RIPTRM_STAT_LOG_COUNT"]] - st[:, C["RIPTRM_STAT_LOG_BASE"]]).astype(np.int64)
-        cap = min(self.cap, int(self.ro.c_opt.log_capacity)) if getattr(self, "ro", None) else self.cap
+        cap = min(self.cap, int(self.ro.c_opt.log_capacity)) if self.ro else self.cap
         kmax = int(k.max()) if self.batch else 0
         slots = self.log_rows(kmax)
         out = []
@@ -364,9 +518,6 @@ class NonnegPCABatch:
         self.ctx.check(self.lib.riptrm_log_rebase(self.ctx.h), "riptrm_log_rebase")
 
     # ---- data ---------------------------------------------------------------------------
-    def _sync_stream(self):
-        self.ctx.set_stream(_stream_handle(self.device))
-
     def load_Z(self, Z) -> "NonnegPCABatch":
         """Z: (batch, n, n) fp64 (numpy or torch).  S_b = Z_b + Z_b^T packed on the device.
         Shared layout: one (n, n) (or (1, n, n)) Z for the whole batch."""
@@ -396,10 +547,9 @@ class NonnegPCABatch:
         """S[slot] <- pack(Z + Z^T) from a contiguous (n, n) device tensor (riptrm_nonnegpca_pack)."""
         assert Zdev.is_contiguous() and Zdev.shape == (self.n, self.n) and Zdev.device == self.device
         self._sync_stream()
-        self.ctx.check(self.lib.riptrm_nonnegpca_pack(self.ctx.h, ctypes.c_void_p(Zdev.data_ptr()), self.n,
-                                                      self.n * self.n, self.n, 1,
-                                                      ctypes.c_void_p(self.S[slot].data_ptr()), self.layout,
-                                                      self.inst_stride), "riptrm_nonnegpca_pack")
+        self.ctx.check(self.lib.riptrm_nonnegpca_pack(self.ctx.h, ptr(Zdev), self.n, self.n * self.n, self.n, 1,
+                                                      ptr(self.S[slot]), self.layout, self.inst_stride),
+                       "riptrm_nonnegpca_pack")
 
     def unpack(self, slot: int) -> np.ndarray:
         """Host copy of S[slot] as a dense n x n matrix (tests / inspection)."""
@@ -424,7 +574,7 @@ class NonnegPCABatch:
 
     def bind(self):
         self._sync_stream()
-        self.ctx.check(self.lib.riptrm_nonnegpca_bind(self.ctx.h, ctypes.c_void_p(self.S.data_ptr()), self.n,
+        self.ctx.check(self.lib.riptrm_nonnegpca_bind(self.ctx.h, ptr(self.S), self.n,
                                                       self.batch, self.layout, 0 if self.shared else self.inst_stride,
                                                       ctypes.c_void_p(self.ws_ptr), self.ws_bytes, self.cap),
                        "riptrm_nonnegpca_bind")
@@ -502,14 +652,6 @@ class NonnegPCABatch:
         return {"ms_per_launch_tile": t.value, "ms_per_launch_super": u.value,
                 "kernel": "k_spass_sup" if k.value == 1 else "k_spass_sym"}
 
-    def trs_skip_stats(self):
-        """(Exact_RepMat subproblems whose CG went through the certified skip test, CGs skipped) since
-        the context was created (riptrm_trs_skip_stats; the tridiagonal path from order 150 on counts
-        here, the eigen-coordinate path below does not)."""
-        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
-        self.ctx.check(self.lib.riptrm_trs_skip_stats(self.ctx.h, ctypes.byref(a), ctypes.byref(b)), "riptrm_trs_skip_stats")
-        return int(a.value), int(b.value)
-
     def persistent_state(self) -> Dict[str, bool]:
         """riptrm_get_persistent: whether the bound shape runs k_persist on this device, and whether
         the current solve / tCG run uses it."""
@@ -525,10 +667,8 @@ class NonnegPCABatch:
         X, Y, V = self._padded(x), self._padded(y), self._padded(v)
         out = torch.zeros_like(X)
         self._sync_stream()
-        self.ctx.check(self.lib.riptrm_nonnegpca_hvp(self.ctx.h, ctypes.c_void_p(X.data_ptr()),
-                                                     ctypes.c_void_p(Y.data_ptr()), float(mu),
-                                                     ctypes.c_void_p(V.data_ptr()), ctypes.c_void_p(out.data_ptr()),
-                                                     self.ld), "riptrm_nonnegpca_hvp")
+        self.ctx.check(self.lib.riptrm_nonnegpca_hvp(self.ctx.h, ptr(X), ptr(Y), float(mu), ptr(V), ptr(out), self.ld),
+                       "riptrm_nonnegpca_hvp")
         torch.cuda.synchronize(self.device)
         return out[:, :self.n]
 
@@ -538,9 +678,7 @@ class NonnegPCABatch:
         X, Zt, St, V = self._padded(x), self._padded(z), self._padded(s), self._padded(v)
         out = torch.zeros_like(X)
         self._sync_stream()
-        self.ctx.check(self.lib.riptrm_nonnegpca_operator_aw(self.ctx.h, ctypes.c_void_p(X.data_ptr()),
-                                                             ctypes.c_void_p(Zt.data_ptr()), ctypes.c_void_p(St.data_ptr()),
-                                                             ctypes.c_void_p(V.data_ptr()), ctypes.c_void_p(out.data_ptr()),
+        self.ctx.check(self.lib.riptrm_nonnegpca_operator_aw(self.ctx.h, ptr(X), ptr(Zt), ptr(St), ptr(V), ptr(out),
                                                              self.ld), "riptrm_nonnegpca_operator_aw")
         torch.cuda.synchronize(self.device)
         return out[:, :self.n]
@@ -550,16 +688,12 @@ class NonnegPCABatch:
         compute_direction :445-452).  Returns (eta, Heta, j, stop_names)."""
         assert self.bound
         X, Y = self._padded(x), self._padded(y)
-        mu_t = torch.as_tensor(np.broadcast_to(np.asarray(mu, dtype=np.float64), (self.batch,)).copy(),
-                               device=self.device)
-        de_t = torch.as_tensor(np.broadcast_to(np.asarray(Delta, dtype=np.float64), (self.batch,)).copy(),
-                               device=self.device)
+        mu_t, de_t = self._dev(mu, (self.batch,)), self._dev(Delta, (self.batch,))
         it = (ctypes.c_int32 * self.batch)()
         st = (ctypes.c_int32 * self.batch)()
         self._sync_stream()
-        self.ctx.check(self.lib.riptrm_tcg(self.ctx.h, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()),
-                                           self.ld, ctypes.c_void_p(mu_t.data_ptr()), ctypes.c_void_p(de_t.data_ptr()),
-                                           it, st, int(max_steps)), "riptrm_tcg")
+        self.ctx.check(self.lib.riptrm_tcg(self.ctx.h, ptr(X), ptr(Y), self.ld, ptr(mu_t), ptr(de_t), it, st,
+                                           int(max_steps)), "riptrm_tcg")
         eta = self.vec(2).clone()
         heta = self.vec(3).clone()
         return eta, heta, np.array(list(it)), [TCG_NAMES[s] for s in st]
@@ -579,11 +713,10 @@ class NonnegPCABatch:
             # eigensolve (RIPTRM.py:686-692 keeps HwNewmatrix the same way)
             cbytes = trs_cache_wanted(self.lib, self.n, self.batch) if ro.c_opt.second_order_stationarity else 0
             if cbytes and (self._trs_cache is None or self._trs_cache.numel() < cbytes + 256):
-                self._trs_cache = torch.empty(cbytes + 256, dtype=torch.uint8, device=self.device)
+                self._trs_cache = aligned_buffer(cbytes, self.device)[0]
             if cbytes:
-                base = self._trs_cache.data_ptr()
-                ptr = base + (-base) % 256
-                self.ctx.check(self.lib.riptrm_trs_bind_cache(self.ctx.h, ctypes.c_void_p(ptr), cbytes, self.n,
+                addr, _ = align256(self._trs_cache)
+                self.ctx.check(self.lib.riptrm_trs_bind_cache(self.ctx.h, ctypes.c_void_p(addr), cbytes, self.n,
                                                               self.batch), "riptrm_trs_bind_cache")
             else:
                 self.ctx.check(self.lib.riptrm_trs_bind_cache(self.ctx.h, None, 0, 0, 0), "riptrm_trs_bind_cache")
@@ -591,23 +724,14 @@ class NonnegPCABatch:
         tabs = ro.device_tables(self.device)
         self._keep = [X, Y] + tabs
         self._sync_stream()
-        self.ctx.check(self.lib.riptrm_solve_begin(self.ctx.h, ctypes.byref(ro.c_opt), ctypes.c_void_p(X.data_ptr()),
-                                                   ctypes.c_void_p(Y.data_ptr()), self.ld,
-                                                   ctypes.c_void_p(tabs[0].data_ptr()), ctypes.c_void_p(tabs[1].data_ptr()),
-                                                   ctypes.c_void_p(tabs[2].data_ptr()), len(ro.mu_tab)),
+        self.ctx.check(self.lib.riptrm_solve_begin(self.ctx.h, ctypes.byref(ro.c_opt), ptr(X), ptr(Y), self.ld,
+                                                   ptr(tabs[0]), ptr(tabs[1]), ptr(tabs[2]), len(ro.mu_tab)),
                        "riptrm_solve_begin")
         self.ro = ro
         self._target = 2 ** 31 - 1
         self._drained = [[] for _ in range(self.batch)]
         self._dropped = np.zeros(self.batch, dtype=np.int64)
         return ro
-
-    def trs_cache_stats(self):
-        """(cache hits, subproblems served) of the HBM Exact_RepMat path since begin()."""
-        h, t = ctypes.c_int64(0), ctypes.c_int64(0)
-        self.ctx.check(self.lib.riptrm_trs_cache_stats(self.ctx.h, ctypes.byref(h), ctypes.byref(t)),
-                       "riptrm_trs_cache_stats")
-        return int(h.value), int(t.value)
 
     def advance(self, steps: int, outer_target: Optional[int] = None) -> int:
         tgt = 2 ** 31 - 1 if outer_target is None else int(outer_target)

@@ -22,6 +22,21 @@ from typing import Any
 import numpy as np
 
 
+_RAISE = object()
+
+
+def cfg_has(cfg, key) -> bool:
+    """Whether a cfg (a dict, or an object with attributes such as an OmegaConf node) has `key`."""
+    return (key in cfg) if isinstance(cfg, dict) else hasattr(cfg, key)
+
+
+def cfg_get(cfg, key, default=_RAISE):
+    """cfg[key] / cfg.key; a missing key gives `default`, or raises KeyError / AttributeError without one."""
+    if default is _RAISE:
+        return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)
+    return cfg.get(key, default) if isinstance(cfg, dict) else getattr(cfg, key, default)
+
+
 @dataclass
 class NonnegPCAProblem:
     Z: Any                      # (n, n) fp64, numpy or torch
@@ -67,25 +82,17 @@ class Coordinator:
 
     def __init__(self, cfg, root: str = "."):
         for key in ("problem_name", "problem_instance", "problem_initialpoint"):
-            if not _has(cfg, key):
+            if not cfg_has(cfg, key):
                 raise AssertionError(f"cfg lacks '{key}'")
         self.cfg = cfg
-        self.dataset_path = os.path.join(root, f"dataset/{_get(cfg, 'problem_name')}/{_get(cfg, 'problem_instance')}")
+        self.dataset_path = os.path.join(root, f"dataset/{cfg_get(cfg, 'problem_name')}/{cfg_get(cfg, 'problem_instance')}")
 
     def run(self) -> NonnegPCAProblem:
         p = self.dataset_path
         dim = int(np.loadtxt(f"{p}/dim.csv"))
         Z = np.loadtxt(f"{p}/Z.csv")
-        x0 = np.loadtxt(f"{p}/initx_{_get(self.cfg, 'problem_initialpoint')}.csv")
+        x0 = np.loadtxt(f"{p}/initx_{cfg_get(self.cfg, 'problem_initialpoint')}.csv")
         y0 = np.loadtxt(f"{p}/initineqLagmult.csv")
         if Z.shape != (dim, dim) or x0.shape != (dim,) or y0.shape != (dim,):
             raise ValueError(f"inconsistent NonnegPCA dataset at {p}")
         return NonnegPCAProblem(Z=Z, initialpoint=x0, initialineqLagmult=y0)
-
-
-def _has(cfg, key):
-    return (key in cfg) if isinstance(cfg, dict) else hasattr(cfg, key)
-
-
-def _get(cfg, key):
-    return cfg[key] if isinstance(cfg, dict) else getattr(cfg, key)

@@ -21,13 +21,14 @@ from __future__ import annotations
 import ctypes
 import math
 from dataclasses import dataclass
-from typing import Any, Dict, List, Optional
+from typing import Any, Dict, Optional
 
 import numpy as np
 import torch
 
 import riptrm_native as N
-from engine import BatchResult, C, NSTAT, NLOG, ResolvedOptions, TCG_NAMES, _stream_handle, assemble_log, resolve_options
+from engine import BatchResult, C, OneLaunchBatch, ResolvedOptions, assemble_log, dxtype_name, ptr, resolve_options
+from problems import cfg_get, cfg_has
 
 LB = 0.01   # coordinator.py:62
 
@@ -376,87 +377,42 @@ def rosenbrock_basis_kind(f) -> int:
     return 1
 
 
-def _has(cfg, key):
-    return (key in cfg) if isinstance(cfg, dict) else hasattr(cfg, key)
-
-
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
-
-
 class Coordinator:
     """coordinator.py:13-95 with the reference's cfg keys n, k, alpha (the problem is built from the
     cfg alone, not from a dataset)."""
 
     def __init__(self, cfg, root: str = "."):
         for key in ("n", "k", "alpha"):
-            if not _has(cfg, key):
+            if not cfg_has(cfg, key):
                 raise AssertionError(f"cfg lacks '{key}'")
         self.cfg = cfg
 
     def run(self) -> RosenbrockProblem:
-        return RosenbrockProblem(n=int(_get(self.cfg, "n")), k=int(_get(self.cfg, "k")),
-                                 alpha=float(_get(self.cfg, "alpha")))
+        return RosenbrockProblem(n=int(cfg_get(self.cfg, "n")), k=int(cfg_get(self.cfg, "k")),
+                                 alpha=float(cfg_get(self.cfg, "alpha")))
 
 
-class RosenbrockBatch:
+class RosenbrockBatch(OneLaunchBatch):
     """A batch of Rosenbrock solves of one shape (n, k) on one GPU: one workgroup per instance, one
     launch.  alpha and lb are per instance."""
 
+    abi = "gr"
+
     def __init__(self, n: int, k: int, batch: int, device: Optional[int] = None, log_capacity: int = 4096):
-        if not torch.cuda.is_available():
-            raise RuntimeError("RosenbrockBatch needs a ROCm GPU (gfx950); there is no CPU fallback")
-        self.lib = N.load()
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self.n, self.k, self.batch, self.cap = int(n), int(k), int(batch), int(log_capacity)
+        super().__init__(batch, log_capacity, device)
+        self.n, self.k = int(n), int(k)
         self.N = self.n * self.k
+        self.point_shape, self.mult_len = (self.n, self.k), self.N
         nbytes = int(self.lib.riptrm_gr_workspace_bytes(self.n, self.k, self.batch, self.cap))
         if nbytes < 0:
             raise ValueError(f"need 1 <= k <= {N.CONST['RIPTRM_GR_KMAX']}, k <= n, "
                              f"n k <= {N.CONST['RIPTRM_GR_NKMAX']}, batch >= 1 (got n = {n}, k = {k}, batch = {batch})")
-        self.ctx = N.Context(self.device.index, _stream_handle(self.device))
-        self.ws = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-        base = self.ws.data_ptr()
-        self._pad = (-base) % 256
-        self.ws_ptr = base + self._pad
-        self.ws_bytes = nbytes
-        self._keep: List[torch.Tensor] = []
-        self.ro: Optional[ResolvedOptions] = None
+        self._allocate(nbytes)
         self._bound = False
         self.trail: Optional[torch.Tensor] = None
 
-    def _view(self, kind: int, shape):
-        off = int(self.lib.riptrm_gr_workspace_offset(self.n, self.k, self.batch, self.cap, kind))
-        count = int(np.prod(shape))
-        start = self._pad + off
-        return self.ws[start:start + count * 8].view(torch.float64).view(*shape)
-
-    def x(self):
-        return self._view(0, (self.batch, self.n, self.k))
-
-    def y(self):
-        return self._view(1, (self.batch, self.N))
-
-    def eta(self):
-        return self._view(2, (self.batch, self.n, self.k))
-
-    def heta(self):
-        return self._view(3, (self.batch, self.n, self.k))
-
-    def stats(self) -> np.ndarray:
-        return self._view(4, (self.batch, NSTAT)).cpu().numpy().copy()
-
-    def log_rows(self, count: int) -> np.ndarray:
-        lg = self._view(5, (self.batch, self.cap, NLOG))
-        return lg[:, :max(0, min(count, self.cap))].cpu().numpy()
-
-    def _dev(self, a, shape) -> torch.Tensor:
-        if isinstance(a, torch.Tensor) and a.device == self.device and a.dtype == torch.float64:
-            return a.reshape(shape).contiguous()   # already on the device: no copy
-        t = torch.as_tensor(np.array(np.broadcast_to(np.asarray(a, dtype=np.float64), shape)))   # a writable copy
-        return t.to(self.device).contiguous()
+    def _offset(self, kind: int) -> int:
+        return self.lib.riptrm_gr_workspace_offset(self.n, self.k, self.batch, self.cap, kind)
 
     def _per_instance(self, a) -> torch.Tensor:
         a = np.asarray(a, dtype=np.float64)
@@ -475,62 +431,29 @@ class RosenbrockBatch:
         pr.n, pr.k = self.n, self.k
         pr.alpha, pr.alpha_stride = self.alphad.data_ptr(), (0 if self.alphad.numel() == 1 else 1)
         pr.lb, pr.lb_stride = self.lbd.data_ptr(), (0 if self.lbd.numel() == 1 else 1)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_bind(self.ctx.h, ctypes.byref(pr), self.batch, ctypes.c_void_p(self.ws_ptr),
-                                               self.ws_bytes, self.cap), "riptrm_gr_bind")
+        self._sync_stream()
+        self._call("bind", ctypes.byref(pr), self.batch, ctypes.c_void_p(self.ws_ptr), self.ws_bytes, self.cap)
         self._prob = pr
         self._bound = True
         self.trail = None   # riptrm_gr_bind unbinds the trail
         return self
 
-    def _mat(self, a) -> torch.Tensor:
-        return self._dev(a, (self.batch, self.n, self.k))
-
-    def _vec(self, a) -> torch.Tensor:
-        return self._dev(a, (self.batch,))
-
-    def hvp(self, x, y, mu, v) -> torch.Tensor:
-        """HwCur(v) at (x, y, mu) per instance; x, v: (batch, n, k), y: (batch, n k)."""
-        X, Y, V, M = self._mat(x), self._dev(y, (self.batch, self.N)), self._mat(v), self._vec(mu)
-        out = torch.zeros_like(X)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_hvp(self.ctx.h, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()),
-                                              ctypes.c_void_p(M.data_ptr()), ctypes.c_void_p(V.data_ptr()),
-                                              ctypes.c_void_p(out.data_ptr())), "riptrm_gr_hvp")
-        torch.cuda.synchronize(self.device)
-        return out
-
-    def tcg(self, x, y, mu, Delta):
-        """tCG at (x, y, mu, Delta) per instance: (eta, Heta, j at exit, stop reason)."""
-        X, Y, M, D = self._mat(x), self._dev(y, (self.batch, self.N)), self._vec(mu), self._vec(Delta)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_tcg(self.ctx.h, None, ctypes.c_void_p(X.data_ptr()),
-                                              ctypes.c_void_p(Y.data_ptr()), ctypes.c_void_p(M.data_ptr()),
-                                              ctypes.c_void_p(D.data_ptr())), "riptrm_gr_tcg")
-        torch.cuda.synchronize(self.device)
-        st = self.stats()
-        js = st[:, C["RIPTRM_STAT_TCG_LAST_J"]].astype(int)
-        stops = [TCG_NAMES[int(s)] for s in st[:, C["RIPTRM_STAT_TCG_LAST_STOP"]]]
-        return self.eta().clone(), self.heta().clone(), js, stops
-
     def ops(self, x, u, y):
         """The manifold pieces per instance: (P_x(u), the retraction of u at x, dist(x, y),
         matrix_rank(x) == k); x, u, y: (batch, n, k)."""
-        X, U, Y = self._mat(x), self._mat(u), self._mat(y)
+        X, U, Y = self._pt(x), self._pt(u), self._pt(y)
         proj, retr = torch.zeros_like(X), torch.zeros_like(X)
         dist = torch.zeros(self.batch, dtype=torch.float64, device=self.device)
         rank = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_ops(self.ctx.h, *(ctypes.c_void_p(t.data_ptr()) for t in
-                                                            (X, U, Y, proj, retr, dist, rank))), "riptrm_gr_ops")
+        self._sync_stream()
+        self._call("ops", *map(ptr, (X, U, Y, proj, retr, dist, rank)))
         torch.cuda.synchronize(self.device)
         return proj, retr, dist, rank.bool()
 
     def launch_info(self) -> Dict[str, int]:
         """Dynamic LDS bytes and threads of a workgroup, workgroups per compute unit."""
         a, b, c = ctypes.c_int32(0), ctypes.c_int32(0), ctypes.c_int32(0)
-        self.ctx.check(self.lib.riptrm_gr_launch_info(self.ctx.h, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)),
-                       "riptrm_gr_launch_info")
+        self._call("launch_info", ctypes.byref(a), ctypes.byref(b), ctypes.byref(c))
         return {"lds_bytes": int(a.value), "threads": int(b.value), "workgroups_per_cu": int(c.value)}
 
     def second_order(self, x, y, active_tol=ACTIVE_TOL, linindtol=LININDTOL, barrier=False, mu=None,
@@ -554,29 +477,21 @@ class RosenbrockBatch:
         if tol.ndim != 0 and tol.shape != (P,):
             raise ValueError(f"active_tol must be a scalar or of shape ({P},)")
         told = self._dev(tol, (1,) if tol.ndim == 0 else (P,))
-        keep = [X, Y, told]
-        instp = None
+        it = mud = None
         if inst is not None:
             ia = np.asarray(inst.cpu() if isinstance(inst, torch.Tensor) else inst, dtype=np.int64)
             if ia.shape != (P,) or (P and (ia.min() < 0 or ia.max() >= self.batch)):
                 raise ValueError(f"inst must hold {P} instance indices in [0, {self.batch})")
             it = torch.as_tensor(ia.astype(np.int32)).to(self.device)
-            keep.append(it)
-            instp = ctypes.c_void_p(it.data_ptr())
         elif P > self.batch:
             raise ValueError(f"{P} points for {self.batch} bound instances: pass inst")
-        mup = None
         if barrier and mu is not None:
-            mud = self._dev(np.asarray(mu, dtype=np.float64), (P,))
-            keep.append(mud)
-            mup = ctypes.c_void_p(mud.data_ptr())
+            mud = self._dev(mu, (P,))
         nf = C["RIPTRM_GR_SO_NFIELDS"]
         out = torch.zeros((P, nf), dtype=torch.float64, device=self.device)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_second_order(
-            self.ctx.h, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()), self.N, instp, P,
-            ctypes.c_void_p(told.data_ptr()), 0 if tol.ndim == 0 else 1, float(linindtol), 1 if barrier else 0, mup,
-            ctypes.c_void_p(out.data_ptr())), "riptrm_gr_second_order")
+        self._sync_stream()
+        self._call("second_order", ptr(X), ptr(Y), self.N, ptr(it), P, ptr(told), 0 if tol.ndim == 0 else 1,
+                   float(linindtol), 1 if barrier else 0, ptr(mud), ptr(out))
         torch.cuda.synchronize(self.device)
         o = out.cpu().numpy()
         res = {name: o[:, C[f"RIPTRM_GR_SO_{name.upper()}"]].copy() for name in ("mineig", "maxeig", "cond")}
@@ -604,17 +519,14 @@ class RosenbrockBatch:
             raise RuntimeError("exact_step: load() first")
         self._check_exact_dim()
         d = self.k * (self.n - self.k)
-        X, Y, M, D = self._mat(x), self._dev(y, (self.batch, self.N)), self._vec(mu), self._vec(Delta)
+        X, Y, M, D = self._pt(x), self._mult(y), self._vec(mu), self._vec(Delta)
         f64 = dict(dtype=torch.float64, device=self.device)
         A, a, dx = torch.zeros((self.batch, d, d), **f64), torch.zeros((self.batch, d), **f64), torch.zeros_like(X)
         lam, me = torch.zeros(self.batch, **f64), torch.zeros(self.batch, **f64)
         kind = torch.zeros(self.batch, dtype=torch.int32, device=self.device)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_exact(self.ctx.h, float(tolhardcase), *(ctypes.c_void_p(t.data_ptr()) for t in
-                                                                              (X, Y, M, D, A, a, dx, kind, lam, me))),
-                       "riptrm_gr_exact")
+        self._sync_stream()
+        self._call("exact", float(tolhardcase), *map(ptr, (X, Y, M, D, A, a, dx, kind, lam, me)))
         torch.cuda.synchronize(self.device)
-        from engine import dxtype_name
         codes = kind.cpu().numpy()
         return {"A": A.cpu().numpy(), "a": a.cpu().numpy(), "dx": dx.cpu().numpy(), "kind_code": codes,
                 "kind": [dxtype_name(int(c)) for c in codes], "lam1": lam.cpu().numpy(), "mineig": me.cpu().numpy(),
@@ -625,8 +537,7 @@ class RosenbrockBatch:
         nbytes = int(self.lib.riptrm_gr_trail_bytes(self.n, self.k, self.batch, self.cap))
         self.trail = torch.zeros((self.batch, self.cap, 2, self.N), dtype=torch.float64, device=self.device)
         assert self.trail.numel() * 8 == nbytes
-        self.ctx.check(self.lib.riptrm_gr_bind_trail(self.ctx.h, ctypes.c_void_p(self.trail.data_ptr()), nbytes),
-                       "riptrm_gr_bind_trail")
+        self._call("bind_trail", ptr(self.trail), nbytes)
         return self
 
     def trail_points(self, st: np.ndarray):
@@ -652,40 +563,16 @@ class RosenbrockBatch:
         if ro.exact:   # opt-in: the reference's matrix depends on its basis here, so the basis must be the pinned one
             rosenbrock_basis_kind(ro.option.get('basisfun'))
             self._check_exact_dim()
-        X, Y = self._mat(x0), self._dev(y0, (self.batch, self.N))
-        tabs = ro.device_tables(self.device)
-        self._keep = [X, Y] + tabs
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_gr_solve(self.ctx.h, ctypes.byref(ro.c_opt), ctypes.c_void_p(X.data_ptr()),
-                                                ctypes.c_void_p(Y.data_ptr()), ctypes.c_void_p(tabs[0].data_ptr()),
-                                                ctypes.c_void_p(tabs[1].data_ptr()), ctypes.c_void_p(tabs[2].data_ptr()),
-                                                len(ro.mu_tab)), "riptrm_gr_solve")
-        self.ro = ro
-        return ro
-
-    def solve(self, x0, y0, option: Dict[str, Any], restart_every: int = 0) -> BatchResult:
-        self.begin(x0, y0, option, restart_every)
-        return self.result()
+        return self._launch(ro, x0, y0)
 
     def result(self) -> BatchResult:
-        torch.cuda.synchronize(self.device)
-        st = self.stats()
-        count = st[:, C["RIPTRM_STAT_LOG_COUNT"]].astype(np.int64)
-        cap = min(self.cap, int(self.ro.c_opt.log_capacity))
-        slots = self.log_rows(int(count.max()) if self.batch else 0)
-        logs, dropped = [], []
-        for b in range(self.batch):   # one launch per solve: no draining, head + latest records kept
-            rows, drop = assemble_log(slots[b], int(count[b]), cap)
-            logs.append(rows.copy())
-            dropped.append(drop)
-        cb = None
+        res = super().result()
         if self.ro.callback_kind == CALLBACK_SECOND_ORDER:   # one launch over every row of every instance
-            X, Y, inst, rows = self.trail_points(st)
+            X, Y, inst, rows = self.trail_points(res.stats)
             so = self.second_order(X, Y, inst=inst)
             cols = second_order_columns(so)
-            cb, at = [], 0
+            res.callback_cols, at = [], 0
             for r in rows:
-                cb.append({key: val[at:at + r] for key, val in cols.items()})
+                res.callback_cols.append({key: val[at:at + r] for key, val in cols.items()})
                 at += r
-        return BatchResult(x=self.x().clone(), y=self.y().clone(), stats=st, raw_log=logs, ro=self.ro,
-                           dropped=np.array(dropped), callback_cols=cb)
+        return res

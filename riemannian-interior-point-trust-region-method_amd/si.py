@@ -13,13 +13,13 @@ import ctypes
 import math
 import os
 from dataclasses import dataclass, field
-from typing import Any, Dict, List, Optional, Sequence
+from typing import Any, Dict, Optional
 
 import numpy as np
-import torch
 
 import riptrm_native as N
-from engine import BatchResult, C, NSTAT, NLOG, ResolvedOptions, TCG_NAMES, _stream_handle, assemble_log, resolve_options
+from engine import C, OneLaunchBatch, ResolvedOptions, bind_trs_scratch, resolve_options, trs_workspace_slots
+from problems import cfg_get, cfg_has
 
 
 def expand_constset(constset) -> np.ndarray:
@@ -215,16 +215,16 @@ class SICoordinator:
 
     def __init__(self, cfg, root: str = "."):
         for key in ("problem_name", "problem_instance", "problem_initialpoint"):
-            if not _has(cfg, key):
+            if not cfg_has(cfg, key):
                 raise AssertionError(f"cfg lacks '{key}'")
         self.cfg = cfg
-        self.dataset_path = os.path.join(root, f"dataset/{_get(cfg, 'problem_name')}/{_get(cfg, 'problem_instance')}")
+        self.dataset_path = os.path.join(root, f"dataset/{cfg_get(cfg, 'problem_name')}/{cfg_get(cfg, 'problem_instance')}")
 
     def run(self) -> SIProblem:
         p = self.dataset_path
-        noisy = bool(_get(self.cfg, "is_X_noisy", True))
-        Xset = list(_get(self.cfg, "Xset", [1, 2, 3, 4, 5]))
-        h = float(_get(self.cfg, "h", 0.02))
+        noisy = bool(cfg_get(self.cfg, "is_X_noisy", True))
+        Xset = list(cfg_get(self.cfg, "Xset", [1, 2, 3, 4, 5]))
+        h = float(cfg_get(self.cfg, "h", 0.02))
         X = XP = None
         for i in Xset:   # coordinator.py:71-88
             Xo = np.loadtxt(f"{p}/{'noisyX' if noisy else 'X'}_{i}.csv")
@@ -235,75 +235,32 @@ class SICoordinator:
         dim = int(np.loadtxt(f"{p}/dim.csv"))
         if X.shape[0] != dim:
             raise ValueError(f"inconsistent StableIdentification dataset at {p}")
-        pt = _get(self.cfg, "problem_initialpoint")
+        pt = cfg_get(self.cfg, "problem_initialpoint")
         x0 = [np.loadtxt(f"{p}/init{c}_{pt}.csv") for c in "JRQ"]
         y0 = np.atleast_1d(np.loadtxt(f"{p}/initineqLagmult.csv"))
         return SIProblem(X=X, XP=XP, h=h, constset=np.loadtxt(f"{p}/constset.csv"), initialpoint=x0,
                          initialineqLagmult=y0)
 
 
-def _has(cfg, key):
-    return (key in cfg) if isinstance(cfg, dict) else hasattr(cfg, key)
-
-
-def _get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
-
-
-class SIBatch:
+class SIBatch(OneLaunchBatch):
     """A batch of StableIdentification solves on one GPU: one workgroup per instance, one launch."""
 
+    abi = "si"
+
     def __init__(self, d: int, N_: int, m: int, batch: int, device: Optional[int] = None, log_capacity: int = 4096):
-        if not torch.cuda.is_available():
-            raise RuntimeError("SIBatch needs a ROCm GPU (gfx950); there is no CPU fallback")
-        self.lib = N.load()
-        self.device = torch.device("cuda", torch.cuda.current_device() if device is None else device)
-        self.d, self.N, self.m, self.batch, self.cap = int(d), int(N_), int(m), int(batch), int(log_capacity)
+        super().__init__(batch, log_capacity, device)
+        self.d, self.N, self.m = int(d), int(N_), int(m)
         self.dd = self.d * self.d
+        self.point_shape, self.mult_len = (3, self.d, self.d), self.m
         nbytes = int(self.lib.riptrm_si_workspace_bytes(self.d, self.N, self.m, self.batch, self.cap))
         if nbytes < 0:
             raise ValueError(f"need 1 <= d <= {N.CONST['RIPTRM_SI_DMAX']}, 1 <= m <= 64 (d <= 8) or "
                              f"m <= 64 ceil(d^2 / 64) (d > 8), batch >= 1")
-        self.ctx = N.Context(self.device.index, _stream_handle(self.device))
-        self.ws = torch.zeros(nbytes + 256, dtype=torch.uint8, device=self.device)
-        base = self.ws.data_ptr()
-        self._pad = (-base) % 256
-        self.ws_ptr = base + self._pad
-        self.ws_bytes = nbytes
-        self._keep: List[torch.Tensor] = []
-        self.ro: Optional[ResolvedOptions] = None
+        self._allocate(nbytes)
         self._trs_ws = None   # (buffer, order, slots): Exact_RepMat at d >= 8 (manifold.dim > 96)
 
-    def _view(self, kind: int, shape):
-        off = int(self.lib.riptrm_si_workspace_offset(self.d, self.N, self.m, self.batch, self.cap, kind))
-        count = int(np.prod(shape))
-        start = self._pad + off
-        return self.ws[start:start + count * 8].view(torch.float64).view(*shape)
-
-    def x(self):
-        return self._view(0, (self.batch, 3, self.d, self.d))
-
-    def y(self):
-        return self._view(1, (self.batch, self.m))
-
-    def eta(self):
-        return self._view(2, (self.batch, 3, self.d, self.d))
-
-    def heta(self):
-        return self._view(3, (self.batch, 3, self.d, self.d))
-
-    def stats(self) -> np.ndarray:
-        return self._view(4, (self.batch, NSTAT)).cpu().numpy().copy()
-
-    def log_rows(self, count: int) -> np.ndarray:
-        lg = self._view(5, (self.batch, self.cap, NLOG))
-        return lg[:, :max(0, min(count, self.cap))].cpu().numpy()
-
-    def _dev(self, a, shape) -> torch.Tensor:
-        t = torch.as_tensor(np.asarray(a, dtype=np.float64)).reshape(shape)
-        return t.to(self.device).contiguous()
+    def _offset(self, kind: int) -> int:
+        return self.lib.riptrm_si_workspace_offset(self.d, self.N, self.m, self.batch, self.cap, kind)
 
     def load(self, X, XP, h: float, cons) -> "SIBatch":
         """X, XP: (d, N) shared by the batch or (batch, d, N); cons: (m, 5) or (batch, m, 5)."""
@@ -320,101 +277,28 @@ class SIBatch:
         pr.data_stride = 0 if shared_data else self.d * self.N
         pr.cons = self.consd.data_ptr()
         pr.cons_stride = 0 if shared_cons else self.m * 5
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_si_bind(self.ctx.h, ctypes.byref(pr), self.batch, ctypes.c_void_p(self.ws_ptr),
-                                               self.ws_bytes, self.cap), "riptrm_si_bind")
+        self._sync_stream()
+        self._call("bind", ctypes.byref(pr), self.batch, ctypes.c_void_p(self.ws_ptr), self.ws_bytes, self.cap)
         self._prob = pr
         return self
 
-    def hvp(self, x, y, mu, v) -> torch.Tensor:
-        X = self._dev(x, (self.batch, 3, self.d, self.d))
-        Y = self._dev(y, (self.batch, self.m))
-        V = self._dev(v, (self.batch, 3, self.d, self.d))
-        M = self._dev(np.broadcast_to(np.asarray(mu, np.float64), (self.batch,)).copy(), (self.batch,))
-        out = torch.zeros_like(X)
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_si_hvp(self.ctx.h, ctypes.c_void_p(X.data_ptr()), ctypes.c_void_p(Y.data_ptr()),
-                                              ctypes.c_void_p(M.data_ptr()), ctypes.c_void_p(V.data_ptr()),
-                                              ctypes.c_void_p(out.data_ptr())), "riptrm_si_hvp")
-        torch.cuda.synchronize(self.device)
-        return out
-
-    def tcg(self, x, y, mu, Delta):
-        X = self._dev(x, (self.batch, 3, self.d, self.d))
-        Y = self._dev(y, (self.batch, self.m))
-        M = self._dev(np.broadcast_to(np.asarray(mu, np.float64), (self.batch,)).copy(), (self.batch,))
-        D = self._dev(np.broadcast_to(np.asarray(Delta, np.float64), (self.batch,)).copy(), (self.batch,))
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_si_tcg(self.ctx.h, None, ctypes.c_void_p(X.data_ptr()),
-                                              ctypes.c_void_p(Y.data_ptr()), ctypes.c_void_p(M.data_ptr()),
-                                              ctypes.c_void_p(D.data_ptr())), "riptrm_si_tcg")
-        torch.cuda.synchronize(self.device)
-        st = self.stats()
-        js = st[:, C["RIPTRM_STAT_TCG_LAST_J"]].astype(int)
-        stops = [TCG_NAMES[int(s)] for s in st[:, C["RIPTRM_STAT_TCG_LAST_STOP"]]]
-        return self.eta().clone(), self.heta().clone(), js, stops
-
     def begin(self, x0, y0, option: Dict[str, Any], restart_every: int = 0) -> ResolvedOptions:
         d = self.d
-        typical = math.sqrt(d * (d - 1) // 2 + d * (d + 1))
-        ro = resolve_options(option, typical, self.cap, restart_every, manvio_classifier=si_manvio_kind)
-        X = self._dev(x0, (self.batch, 3, d, d))
-        Y = self._dev(y0, (self.batch, self.m))
         tdim = d * (d - 1) // 2 + d * (d + 1)
+        ro = resolve_options(option, math.sqrt(tdim), self.cap, restart_every, manvio_classifier=si_manvio_kind)
         if ro.exact and tdim > C["RIPTRM_TRS_DIM_MAX"]:
             # d >= 8: the subproblem's matrix (manifold.dim squared) no longer fits LDS; instances park
             # at each subproblem and the host's batched service (riptrm_trs_big.hip) solves them in
             # caller-owned HBM scratch, one slot per instance of a pass (riptrm_trs_bind_workspace)
-            from engine import bind_trs_scratch, trs_workspace_slots
             slots = trs_workspace_slots(self.lib, tdim, self.batch)
             self._trs_ws = bind_trs_scratch(self.ctx, self.lib, self.device, self._trs_ws, tdim, slots)
-        tabs = ro.device_tables(self.device)
-        self._keep = [X, Y] + tabs
-        self.ctx.set_stream(_stream_handle(self.device))
-        self.ctx.check(self.lib.riptrm_si_solve(self.ctx.h, ctypes.byref(ro.c_opt), ctypes.c_void_p(X.data_ptr()),
-                                                ctypes.c_void_p(Y.data_ptr()), ctypes.c_void_p(tabs[0].data_ptr()),
-                                                ctypes.c_void_p(tabs[1].data_ptr()), ctypes.c_void_p(tabs[2].data_ptr()),
-                                                len(ro.mu_tab)), "riptrm_si_solve")
-        self.ro = ro
-        return ro
-
-    def trs_skip_stats(self):
-        """(subproblems whose CG was decided on their eigenpairs, CGs skipped) since the context was
-        created (riptrm_trs_skip_stats)."""
-        a, b = ctypes.c_int64(0), ctypes.c_int64(0)
-        self.ctx.check(self.lib.riptrm_trs_skip_stats(self.ctx.h, ctypes.byref(a), ctypes.byref(b)), "riptrm_trs_skip_stats")
-        return int(a.value), int(b.value)
-
-    def trs_cache_stats(self):
-        """(subproblems served from the keyed eigendecomposition cache, subproblems served) of the
-        last solve on the HBM Exact_RepMat path (riptrm_trs_cache_stats)."""
-        h, t = ctypes.c_int64(0), ctypes.c_int64(0)
-        self.ctx.check(self.lib.riptrm_trs_cache_stats(self.ctx.h, ctypes.byref(h), ctypes.byref(t)), "riptrm_trs_cache_stats")
-        return int(h.value), int(t.value)
+        return self._launch(ro, x0, y0)
 
     def profile_enable(self, on: bool = True):
-        self.ctx.check(self.lib.riptrm_si_profile_enable(self.ctx.h, 1 if on else 0), "riptrm_si_profile_enable")
+        self._call("profile_enable", 1 if on else 0)
 
     def profile_read(self) -> Dict[str, float]:
         out = (ctypes.c_double * C["RIPTRM_SI_PROF_NFIELDS"])()
-        self.ctx.check(self.lib.riptrm_si_profile_read(self.ctx.h, out), "riptrm_si_profile_read")
+        self._call("profile_read", out)
         names = ("total", "prepare", "tcg", "hvp", "trial", "eval")
         return {k: float(out[i]) for i, k in enumerate(names)}
-
-    def solve(self, x0, y0, option: Dict[str, Any], restart_every: int = 0) -> BatchResult:
-        self.begin(x0, y0, option, restart_every)
-        return self.result()
-
-    def result(self) -> BatchResult:
-        torch.cuda.synchronize(self.device)
-        st = self.stats()
-        count = st[:, C["RIPTRM_STAT_LOG_COUNT"]].astype(np.int64)
-        cap = min(self.cap, int(self.ro.c_opt.log_capacity))
-        slots = self.log_rows(int(count.max()) if self.batch else 0)
-        logs, dropped = [], []
-        for b in range(self.batch):   # one launch per solve: no draining, head + latest records kept
-            rows, drop = assemble_log(slots[b], int(count[b]), cap)
-            logs.append(rows.copy())
-            dropped.append(drop)
-        return BatchResult(x=self.x().clone(), y=self.y().clone(), stats=st, raw_log=logs, ro=self.ro,
-                           dropped=np.array(dropped))

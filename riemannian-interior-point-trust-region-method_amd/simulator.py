@@ -19,13 +19,7 @@ from typing import Any, Dict, Iterable, List
 
 import numpy as np
 
-from problems import Coordinator, manviofun
-
-
-def _cfg_get(cfg, key, default=None):
-    if isinstance(cfg, dict):
-        return cfg.get(key, default)
-    return getattr(cfg, key, default)
+from problems import Coordinator, cfg_get, manviofun
 
 
 def save_output(output_path: str, solver_name: str, output) -> List[str]:
@@ -55,32 +49,32 @@ class Simulator:
 
     def __init__(self, cfg, root: str = "."):
         for key in ("problem_name", "problem_instance", "problem_initialpoint", "solver_name", "solver_option"):
-            if _cfg_get(cfg, key) is None:
+            if cfg_get(cfg, key, None) is None:
                 raise AssertionError(f"cfg lacks '{key}'")
         self.cfg = cfg
         self.root = root
         self.logger = logging.getLogger(__name__)
 
     def solver_option(self, name: str) -> Dict[str, Any]:
-        so = _cfg_get(self.cfg, "solver_option")
-        option = copy.deepcopy(dict(_cfg_get(so, "common", {}) or {}))
-        specific = _cfg_get(so, name)
+        so = cfg_get(self.cfg, "solver_option")
+        option = copy.deepcopy(dict(cfg_get(so, "common", {}) or {}))
+        specific = cfg_get(so, name, None)
         if specific is not None:
             option.update(dict(specific))
         option["manviofun"] = manviofun          # src/NonnegPCA/simulator.py:17-19
         return option
 
     def output_path(self) -> str:
-        p = _cfg_get(self.cfg, "output_path")
+        p = cfg_get(self.cfg, "output_path", None)
         if p is None:
-            p = (f"intermediate/{_cfg_get(self.cfg, 'problem_name')}/{_cfg_get(self.cfg, 'problem_instance')}/"
-                 f"{_cfg_get(self.cfg, 'problem_initialpoint')}")
+            p = (f"intermediate/{cfg_get(self.cfg, 'problem_name')}/{cfg_get(self.cfg, 'problem_instance')}/"
+                 f"{cfg_get(self.cfg, 'problem_initialpoint')}")
         return os.path.join(self.root, p)
 
     def run(self):
         problem = Coordinator(self.cfg, root=self.root).run()
         outputs = []
-        names: Iterable[str] = _cfg_get(self.cfg, "solver_name")
+        names: Iterable[str] = cfg_get(self.cfg, "solver_name")
         if isinstance(names, str):
             names = [names]
         for name in names:

@@ -7,13 +7,12 @@ GPU (shape (batch, n, p), fp64, contiguous).  No CPU fallback.
 """
 from __future__ import annotations
 
-import ctypes
 import math
 
 import torch
 
 import riptrm_native as N
-from engine import _stream_handle
+from engine import _stream_handle, ptr
 
 
 class StiefelBatch:
@@ -39,21 +38,20 @@ class StiefelBatch:
         self.ctx.set_stream(_stream_handle(self.device))
         return ts[0].shape[0]
 
-    def _ptr(self, t):
-        return ctypes.c_void_p(t.data_ptr())
+    _ptr = staticmethod(ptr)   # the name tests call
 
     def inner_product(self, X, U, V) -> torch.Tensor:
         B = self._chk(X, U, V)
         out = torch.empty(B, dtype=torch.float64, device=self.device)
-        self.ctx.check(self.lib.riptrm_stiefel_inner(self.ctx.h, self.n, self.p, B, self.n * self.p, self._ptr(X),
-                                                     self._ptr(U), self._ptr(V), self._ptr(out)), "riptrm_stiefel_inner")
+        self.ctx.check(self.lib.riptrm_stiefel_inner(self.ctx.h, self.n, self.p, B, self.n * self.p, ptr(X),
+                                                     ptr(U), ptr(V), ptr(out)), "riptrm_stiefel_inner")
         return out
 
     def projection(self, X, U) -> torch.Tensor:
         B = self._chk(X, U)
         out = torch.empty_like(U)
-        self.ctx.check(self.lib.riptrm_stiefel_proj(self.ctx.h, self.n, self.p, B, self.n * self.p, self._ptr(X),
-                                                    self._ptr(U), self._ptr(out)), "riptrm_stiefel_proj")
+        self.ctx.check(self.lib.riptrm_stiefel_proj(self.ctx.h, self.n, self.p, B, self.n * self.p, ptr(X),
+                                                    ptr(U), ptr(out)), "riptrm_stiefel_proj")
         return out
 
     to_tangent_space = projection
@@ -62,14 +60,14 @@ class StiefelBatch:
     def retraction(self, X, U) -> torch.Tensor:
         B = self._chk(X, U)
         out = torch.empty_like(X)
-        self.ctx.check(self.lib.riptrm_stiefel_retr(self.ctx.h, self.n, self.p, B, self.n * self.p, self._ptr(X),
-                                                    self._ptr(U), self._ptr(out)), "riptrm_stiefel_retr")
+        self.ctx.check(self.lib.riptrm_stiefel_retr(self.ctx.h, self.n, self.p, B, self.n * self.p, ptr(X),
+                                                    ptr(U), ptr(out)), "riptrm_stiefel_retr")
         return out
 
     def euclidean_to_riemannian_hessian(self, X, G, H, U) -> torch.Tensor:
         B = self._chk(X, G, H, U)
         out = torch.empty_like(X)
         self.ctx.check(self.lib.riptrm_stiefel_ehess2rhess(self.ctx.h, self.n, self.p, B, self.n * self.p,
-                                                           self._ptr(X), self._ptr(G), self._ptr(H), self._ptr(U),
-                                                           self._ptr(out)), "riptrm_stiefel_ehess2rhess")
+                                                           ptr(X), ptr(G), ptr(H), ptr(U),
+                                                           ptr(out)), "riptrm_stiefel_ehess2rhess")
         return out

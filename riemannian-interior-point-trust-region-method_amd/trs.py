@@ -11,14 +11,13 @@ pass when the scratch budget allows).  Only B = I is supported — the one call 
 """
 from __future__ import annotations
 
-import ctypes
 from typing import Tuple
 
 import numpy as np
 import torch
 
 import riptrm_native as N
-from engine import _stream_handle, trs_workspace_slots
+from engine import _stream_handle, bind_trs_scratch, ptr, trs_workspace_slots
 
 C = N.CONST
 KIND_NAMES = {C["RIPTRM_TRS_BOUNDARY"]: "boundary", C["RIPTRM_TRS_INTERIOR"]: "interior",
@@ -45,16 +44,10 @@ def bind_trs_workspace(ctx: N.Context, device: torch.device, order: int, slots: 
     tensor is kept alive with the context."""
     key = (id(ctx), device.index)
     have = _ws.get(key)
-    if have is None or have[1] < order or have[2] < slots:
-        nbytes = int(ctx.lib.riptrm_trs_workspace_bytes(int(order), int(slots)))
-        buf = torch.empty(nbytes + 256, dtype=torch.uint8, device=device)
-        have = _ws[key] = (buf, int(order), int(slots))
-    buf, o, sl = have
-    base = buf.data_ptr()
-    ptr = base + (-base) % 256
-    ctx.check(ctx.lib.riptrm_trs_bind_workspace(ctx.h, ctypes.c_void_p(ptr), buf.numel() - (ptr - base), o, sl),
-              "riptrm_trs_bind_workspace")
-    return buf
+    if have is not None and have[1] >= order and have[2] >= slots:
+        order, slots = have[1:]   # a kept buffer stays bound at the size it was made for
+    have = _ws[key] = bind_trs_scratch(ctx, ctx.lib, device, have, order, slots)
+    return have[0]
 
 
 def trs_gep_batched(A: torch.Tensor, a: torch.Tensor, Delta: torch.Tensor, tolhardcase: float = 1e-8
@@ -79,9 +72,8 @@ def trs_gep_batched(A: torch.Tensor, a: torch.Tensor, Delta: torch.Tensor, tolha
     lam1 = torch.empty(B, dtype=torch.float64, device=dev)
     kind = torch.empty(B, dtype=torch.int32, device=dev)
     mineig = torch.empty(B, dtype=torch.float64, device=dev)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    ctx.check(ctx.lib.riptrm_trs_gep(ctx.h, dim, B, p(A), dim, dim * dim, p(a), dim, p(Delta), float(tolhardcase),
-                                     p(x), p(lam1), p(kind), p(mineig)), "riptrm_trs_gep")
+    ctx.check(ctx.lib.riptrm_trs_gep(ctx.h, dim, B, ptr(A), dim, dim * dim, ptr(a), dim, ptr(Delta), float(tolhardcase),
+                                     ptr(x), ptr(lam1), ptr(kind), ptr(mineig)), "riptrm_trs_gep")
     return x, lam1, kind, mineig
 
 
@@ -114,8 +106,7 @@ def sym_eig(A: torch.Tensor, vectors: bool = True) -> Tuple[torch.Tensor, torch.
     w = torch.empty((B, dim), dtype=torch.float64, device=A.device)
     info = torch.empty(B, dtype=torch.int32, device=A.device)
     ctx = _context(A.device)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    ctx.check(ctx.lib.riptrm_sym_eig(ctx.h, dim, B, p(V), dim, dim * dim, p(w), dim, p(info), 1 if vectors else 0),
+    ctx.check(ctx.lib.riptrm_sym_eig(ctx.h, dim, B, ptr(V), dim, dim * dim, ptr(w), dim, ptr(info), 1 if vectors else 0),
               "riptrm_sym_eig")
     return w, (V if vectors else None), info
 
@@ -135,7 +126,6 @@ def sym_tridiag(A: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor, torch.Tens
     e = torch.zeros((B, dim), dtype=torch.float64, device=A.device)
     info = torch.empty(B, dtype=torch.int32, device=A.device)
     ctx = _context(A.device)
-    p = lambda t: ctypes.c_void_p(t.data_ptr())  # noqa: E731
-    ctx.check(ctx.lib.riptrm_sym_tridiag(ctx.h, dim, B, p(A), dim, dim * dim, p(d), p(e), dim, p(info)),
+    ctx.check(ctx.lib.riptrm_sym_tridiag(ctx.h, dim, B, ptr(A), dim, dim * dim, ptr(d), ptr(e), dim, ptr(info)),
               "riptrm_sym_tridiag")
     return d, e, info
