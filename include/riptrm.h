@@ -217,6 +217,17 @@ int64_t riptrm_workspace_bytes(int32_t n, int32_t batch, int32_t log_capacity, i
  * 4 = stats (batch x RIPTRM_STAT_NFIELDS doubles), 5 = log (batch x capacity x NFIELDS). */
 int64_t riptrm_workspace_offset(int32_t n, int32_t batch, int32_t log_capacity, int32_t layout,
                                 int32_t kind);
+/* Stored bytes of super-tile unit `unit` (0 .. nsup - 1) of one symmetric-tile instance; -1 for a
+ * bad argument. */
+int64_t riptrm_sup_unit_bytes(int32_t n, int32_t unit);
+/* Host mirror of the super-tile S-pass kernel's static deal (the same mapping function the kernel
+ * calls): a launch of `grid` workgroups over `nact` active slots.  balanced = 0: index order (the
+ * default); 1: the units largest first, dealt back and forth (RIPTRM_SUP_BALANCED=1).  Walks
+ * workgroup 0's items in its own order, then workgroup 1's, ...; writes the first `cap` of them
+ * (workgroup, slot, unit) and returns how many there are (nact x nsup when the deal is complete);
+ * -1 for a bad argument. */
+int64_t riptrm_sup_deal(int32_t n, int32_t balanced, int32_t nact, int32_t grid, int32_t* wg, int32_t* slot,
+                        int32_t* unit, int64_t cap);
 
 /* ---- data preparation ---- */
 /* S_b <- pack(Z_b + Z_b^T) for b < count: Z_b is n x n row-major with leading dimension ldz at

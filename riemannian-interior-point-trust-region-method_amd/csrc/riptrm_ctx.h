@@ -42,11 +42,19 @@ struct riptrm_ctx {
                               // 2 = super-tile always, 3 = automatic with bind-time timing
   int sup_auto = 1;           // kind 3: the super-tile kernel won the bind-time calibration
   float spass_cal_ms[2] = {0.0f, 0.0f};   // calibration: ms per launch of the per-tile / super-tile kernel
+  std::vector<int32_t> sup_perm;   // host copy of the workspace's [perm] region (the upload's source)
   // optional HIP-event timing of every k_gemv / k_state launch (riptrm_profile_*)
+  // Two event pools: a chunk of lock-step iterations records into pool ev_cur; its pairs are folded
+  // into the totals while the next chunk (recording into the other pool) runs, not while the chip
+  // waits for the host between chunks (prof_fold / prof_collect in riptrm_kernels.hip)
   bool prof = false;
-  std::vector<hipEvent_t> ev_pool;
-  std::vector<std::pair<int, int>> ev_gemv, ev_state;  // (start, end) indices into ev_pool
-  int ev_used = 0;
+  std::vector<hipEvent_t> ev_pool[2];
+  std::vector<std::pair<int, int>> ev_gemv[2], ev_state[2];  // (start, end) indices into the pool
+  int ev_used[2] = {0, 0};
+  int ev_cur = 0;
+  // with profiling on, the groups' last S-pass end (timing) events of the current chunk: the other
+  // group's next pass waits on that event itself instead of a second marker behind it
+  hipEvent_t pass_end[2] = {nullptr, nullptr};
   double gemv_ms = 0.0, state_ms = 0.0;
   int64_t gemv_n = 0, state_n = 0;
   // hipGraph of GRAPH_STEPS lock-step iterations (single group, no profiling): replayed instead of

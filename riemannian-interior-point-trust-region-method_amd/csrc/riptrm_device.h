@@ -10,6 +10,8 @@
 //   [lists]    4 x batch int32                    active-instance lists (2 groups x ping-pong)
 //   [req]      batch int32                        right-hand sides wanted per instance (1|2)
 //   [counters] 4 int32                            list lengths (2 groups x ping-pong)
+//   [perm]     nsup int32                         super-tile units, largest first (after the persistent regions;
+//                                                 written when RIPTRM_SUP_BALANCED=1)
 #pragma once
 #include <stdint.h>
 #include "../../include/riptrm.h"
@@ -83,6 +85,7 @@ struct Layout {
   // for batch x (reps - 1) replicas, the second parity of the partial grid, and the sync block
   // (per-instance arrival counters + published clocks + the timeout flag; zeroed before every launch)
   int64_t off_rvec, off_rstate, off_rstats, off_rreq, off_pbuf2, off_sync, sync_bytes, off_tgrid, tgrid_bytes;
+  int64_t off_perm;    // nsup int32: the super-tile S-pass's size-sorted unit order (symmetric-tile layout)
   int64_t total;
 };
 
@@ -145,6 +148,48 @@ inline int64_t s_elems_of(int32_t n, int32_t layout) {
   return rows_of(n) * ld_of(n);
 }
 
+// upper-triangle index t (row by row) of an nt x nt grid -> (I, J), I <= J
+__host__ __device__ __forceinline__ void tile_ij(int t, int nt, int& I, int& J) {
+  int i = 0, rem = t, len = nt;
+  while (rem >= len) { rem -= len; ++i; --len; }
+  I = i;
+  J = i + rem;
+}
+
+// stored bytes of super-tile unit u of an instance: its SB x SB block's stored tiles (J >= I),
+// each rows x cols doubles with the last tile row / column wl wide
+inline int64_t sup_unit_bytes(int32_t n, int u) {
+  const int nt = nt_of(n), wl = edge_w_of(n);
+  int Pq, Qq;
+  tile_ij(u, nst_of(n), Pq, Qq);
+  int64_t e = 0;
+  for (int I = SB * Pq; I < SB * Pq + SB && I < nt; ++I)
+    for (int J = SB * Qq; J < SB * Qq + SB && J < nt; ++J)
+      if (J >= I) e += (int64_t)(I == nt - 1 ? wl : TS) * (J == nt - 1 ? wl : TS);
+  return e * 8;
+}
+
+// Static deal of k_spass_sup.  A launch over nact active slots has nact * nsup items.  Balanced
+// order (perm != nullptr): item q is unit perm[q / nact] of slot q % nact, so the items run size
+// class by size class, largest units first, and workgroup g of G takes item k G + g in even rounds
+// k and k G + (G - 1 - g) in odd ones: the workgroup that got the larger item of one round gets
+// the smaller of the next, and the launch's tail is made of the smallest units.  Index order
+// (perm == nullptr): item q is unit q % nsup of slot q / nsup, dealt k G + g in every round.  A
+// workgroup is done at its first item >= nact * nsup (later rounds only give larger items).
+__host__ __device__ inline int sup_deal_item(int k, int g, int G, bool balanced) {
+  return k * G + ((balanced && (k & 1)) ? G - 1 - g : g);
+}
+__host__ __device__ inline void sup_item_unit(int q, int nact, int nsup, const int32_t* perm, int& slot, int& unit) {
+  if (perm) {
+    const int c = q / nact;
+    slot = q - c * nact;
+    unit = perm[c];
+  } else {
+    slot = q / nsup;
+    unit = q - slot * nsup;
+  }
+}
+
 // Persistent lock-step mode (k_persist; symmetric-tile layout, tCG): one 512-thread workgroup per
 // stored tile of every instance, all co-resident (one per CU: the tile sits in 128 KiB of LDS), so
 // at most PERSIST_MAX_WG workgroups; every workgroup of an instance runs a private replica of the
@@ -187,6 +232,8 @@ inline Layout make_layout(int32_t n, int32_t batch, int32_t cap, int32_t layout)
   L.off_tgrid = o;
   L.tgrid_bytes = L.reps > 0 ? (int64_t)2 * batch * nt_of(n) * nt_of(n) * TS * 16 : 0;
   o += L.tgrid_bytes;                                                    o = round_up(o, 256);
+  L.off_perm = o;
+  if (layout == RIPTRM_LAYOUT_SYMTILE) o += nsup_of(n) * 4;              o = round_up(o, 256);
   L.total = o;
   return L;
 }
@@ -205,6 +252,8 @@ struct DevParams {
   int32_t nst, nsup;    // super-blocks per dimension, super-tile units per instance
   int32_t smode;        // per launch: 0 = tile S-pass (grid [nt][nt][TS]), 1 = super-tile ([nst][nst][SW])
   int32_t sup_dyn;      // k_spass_sup: 1 = units handed out by a ticket counter (cnt[8 + list]), 0 = static
+  const int32_t* sup_perm;   // static deal: nullptr = the units in index order, u = g, g + G, ... (default);
+                        // else the units largest first, dealt back and forth (RIPTRM_SUP_BALANCED=1)
   double* pbuf;         // S-pass partial sums: 2 x pbatch x pgrid_of(n) (symmetric-tile layout),
                         // MM_KZ x 2 x batch x ld (shared layout)
   int32_t pbatch;       // instances of the partial grid (= batch; the persistent replicas' parameter

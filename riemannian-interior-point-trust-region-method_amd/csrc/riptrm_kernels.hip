@@ -13,6 +13,7 @@
 #include <math.h>
 #include <string>
 #include <vector>
+#include <algorithm>
 #include <cstring>
 #include <cstdio>
 #include <type_traits>
@@ -212,13 +213,6 @@ __global__ void __launch_bounds__(GV_THREADS) k_gemv(DevParams P, int list_in, i
 // partial-sum grid P[b][I][J][0..127] (every slot written exactly once per pass) that the
 // state kernel sums in fixed J order: deterministic, no atomics.
 // ------------------------------------------------------------------------------------------
-__device__ __forceinline__ void tile_ij(int t, int nt, int& I, int& J) {
-  int i = 0, rem = t, len = nt;
-  while (rem >= len) { rem -= len; ++i; --len; }
-  I = i;
-  J = i + rem;
-}
-
 // gfx950 half exchanges on one double: swap32 trades lanes 32-63 of a with lanes 0-31 of b,
 // swap16 trades the odd 16-lane rows of a with the even rows of b (v_permlane{32,16}_swap_b32).
 __device__ __forceinline__ void swap32(double& a, double& b) {
@@ -516,7 +510,9 @@ __device__ __forceinline__ void sup_flush(const DevParams& P, const double* outb
   __syncthreads();
 }
 
-// Unit order: static (u = g, g + G, ...) or, with P.sup_dyn, tickets from a per-list counter
+// Unit order: a static deal (riptrm_device.h sup_deal_item / sup_item_unit: the units largest first
+// and dealt back and forth, so every workgroup gets nearly the same bytes at any active count; or,
+// without P.sup_perm, in index order u = g, g + G, ...) or, with P.sup_dyn, tickets from a per-list counter
 // (cnt[8 + list_in]): a workgroup takes its next unit when it finishes one, so CUs that also run
 // the other group's state kernel, and units of 3 vs 4 tiles or two right-hand sides, no longer
 // decide the launch's end.  The next ticket is fetched at the start of the current unit (its
@@ -535,20 +531,23 @@ __global__ void __launch_bounds__(SP_THREADS, 1) k_spass_sup(DevParams P, int li
   const bool dyn = P.sup_dyn != 0;
   unsigned int* tick = (unsigned int*)P.cnt + 8 + list_in;
   unsigned int* done = (unsigned int*)P.cnt + 12 + list_in;
-  int u = blockIdx.x;
+  const int32_t* perm = dyn ? nullptr : P.sup_perm;   // tickets hand the units out in index order
+  int q = blockIdx.x, round = 0;   // item of the launch (the static deal's round 0 is item g)
   if (dyn) {
     if (threadIdx.x == 0) tick_next = (int)atomicAdd(tick, 1u);
     __syncthreads();
-    u = tick_next;
+    q = tick_next;
   }
-  while (u < total) {
+  while (q < total) {
     unsigned int pre = 0;
     if (dyn && threadIdx.x == 0) pre = atomicAdd(tick, 1u);   // next unit, in flight during this one
-    const int slot = u / P.nsup;
+    int slot, unit;
+    sup_item_unit(q, nact, P.nsup, perm, slot, unit);
+    const int u = slot * P.nsup + unit;   // what sup_flush decodes
     const int32_t e = P.lists[list_in * P.batch + slot];
     const int b = le_b(e), nr = le_nrhs(e);
     int Pq, Qq;
-    tile_ij(u - slot * P.nsup, P.nst, Pq, Qq);
+    tile_ij(unit, P.nst, Pq, Qq);
     if (used + nr * 2 * SW > SUP_OCAP) {
       sup_flush(P, outb, meta, nslot, list_in);
       used = 0;
@@ -570,9 +569,9 @@ __global__ void __launch_bounds__(SP_THREADS, 1) k_spass_sup(DevParams P, int li
       __syncthreads();                 // every thread has read tick_next (and meta is ordered)
       if (threadIdx.x == 0) tick_next = (int)pre;
       __syncthreads();
-      u = tick_next;
+      q = tick_next;
     } else {
-      u += gridDim.x;
+      q = sup_deal_item(++round, (int)blockIdx.x, (int)gridDim.x, perm != nullptr);
     }
   }
   if (nslot > 0) sup_flush(P, outb, meta, nslot, list_in);
@@ -3008,35 +3007,83 @@ __global__ void __launch_bounds__(ST_THREADS) k_aw_epi(DevParams P, const double
 using namespace riptrm;
 
 static hipEvent_t prof_event(riptrm_ctx* c, int* idx) {
-  if (c->ev_used == (int)c->ev_pool.size()) {
+  const int p = c->ev_cur;
+  if (c->ev_used[p] == (int)c->ev_pool[p].size()) {
     hipEvent_t e;
-    if (hipEventCreate(&e) != hipSuccess) return nullptr;
-    c->ev_pool.push_back(e);
+    // agent scope, like every event of the lock-step chain (riptrm_ctx_create): nothing the host reads hangs on them
+    if (hipEventCreateWithFlags(&e, hipEventDisableSystemFence) != hipSuccess) return nullptr;
+    c->ev_pool[p].push_back(e);
   }
-  *idx = c->ev_used;
-  return c->ev_pool[c->ev_used++];
+  *idx = c->ev_used[p];
+  return c->ev_pool[p][c->ev_used[p]++];
 }
 
-// after a stream sync: fold the recorded pairs into the running totals
-static void prof_collect(riptrm_ctx* c) {
-  for (auto& pr : c->ev_gemv) {
+// fold pool p's recorded pairs into the running totals; every event of the pool has completed
+static void prof_fold(riptrm_ctx* c, int p) {
+  for (auto& pr : c->ev_gemv[p]) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev_pool[pr.first], c->ev_pool[pr.second]) == hipSuccess) c->gemv_ms += ms;
+    if (hipEventElapsedTime(&ms, c->ev_pool[p][pr.first], c->ev_pool[p][pr.second]) == hipSuccess) c->gemv_ms += ms;
     c->gemv_n++;
   }
-  for (auto& pr : c->ev_state) {
+  for (auto& pr : c->ev_state[p]) {
     float ms = 0.f;
-    if (hipEventElapsedTime(&ms, c->ev_pool[pr.first], c->ev_pool[pr.second]) == hipSuccess) c->state_ms += ms;
+    if (hipEventElapsedTime(&ms, c->ev_pool[p][pr.first], c->ev_pool[p][pr.second]) == hipSuccess) c->state_ms += ms;
     c->state_n++;
   }
-  c->ev_gemv.clear();
-  c->ev_state.clear();
-  c->ev_used = 0;
+  c->ev_gemv[p].clear();
+  c->ev_state[p].clear();
+  c->ev_used[p] = 0;
+}
+
+// after a stream sync: fold everything recorded so far, the older pool first
+static void prof_collect(riptrm_ctx* c) {
+  prof_fold(c, c->ev_cur ^ 1);
+  prof_fold(c, c->ev_cur);
+  c->pass_end[0] = c->pass_end[1] = nullptr;
+}
+
+// the units of one instance sorted by stored bytes, largest first, equal sizes in index order
+static void sup_perm_of(int32_t n, std::vector<int32_t>& perm) {
+  const int nsup = (int)nsup_of(n);
+  std::vector<int64_t> bytes(nsup);
+  perm.resize(nsup);
+  for (int u = 0; u < nsup; ++u) {
+    perm[u] = u;
+    bytes[u] = sup_unit_bytes(n, u);
+  }
+  std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return bytes[a] > bytes[b]; });
 }
 
 extern "C" {
 
 int riptrm_abi_version(void) { return RIPTRM_ABI_VERSION; }
+
+int64_t riptrm_sup_unit_bytes(int32_t n, int32_t unit) {
+  if (n < 2 || unit < 0 || unit >= nsup_of(n)) return -1;
+  return sup_unit_bytes(n, unit);
+}
+
+int64_t riptrm_sup_deal(int32_t n, int32_t balanced, int32_t nact, int32_t grid, int32_t* wg, int32_t* slot, int32_t* unit,
+                        int64_t cap) {
+  if (n < 2 || nact < 1 || grid < 1 || cap < 0 || (cap > 0 && (!wg || !slot || !unit))) return -1;
+  const int nsup = (int)nsup_of(n);
+  const int64_t total = (int64_t)nact * nsup;
+  if (total > INT32_MAX) return -1;
+  std::vector<int32_t> perm;
+  if (balanced) sup_perm_of(n, perm);
+  int64_t cnt = 0;
+  for (int g = 0; g < grid; ++g)
+    for (int k = 0;; ++k) {
+      const int q = sup_deal_item(k, g, grid, balanced != 0);
+      if (q >= total) break;
+      if (cnt < cap) {
+        wg[cnt] = g;
+        sup_item_unit(q, nact, nsup, balanced ? perm.data() : nullptr, slot[cnt], unit[cnt]);
+      }
+      ++cnt;
+    }
+  return cnt;
+}
 
 int riptrm_ctx_create(riptrm_ctx** out, int device, void* stream) {
   if (!out) return RIPTRM_E_ARG;
@@ -3055,11 +3102,14 @@ int riptrm_ctx_create(riptrm_ctx** out, int device, void* stream) {
     c->clock_hz = (double)khz * 1000.0;
   int ncu = 0;
   if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->ncu = ncu;
+  // the chain's events order device work against device work only (the host waits on streams):
+  // agent scope, no system-scope fence at every hand-over between the groups' S-passes
+  const unsigned ef = hipEventDisableTiming | hipEventDisableSystemFence;
   if (hipSetDevice(device) != hipSuccess || hipStreamCreateWithFlags(&c->own_stream, hipStreamNonBlocking) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_pass[0], hipEventDisableTiming) != hipSuccess ||
-      hipEventCreateWithFlags(&c->ev_pass[1], hipEventDisableTiming) != hipSuccess) {
+      hipEventCreateWithFlags(&c->ev_fork, ef) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_join, ef) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_pass[0], ef) != hipSuccess ||
+      hipEventCreateWithFlags(&c->ev_pass[1], ef) != hipSuccess) {
     riptrm_ctx_destroy(c);
     return RIPTRM_E_HIP;
   }
@@ -3073,7 +3123,8 @@ int riptrm_ctx_destroy(riptrm_ctx* ctx) {
     if (ctx->si) riptrm_si_release(ctx->si);
     if (ctx->gr) riptrm_gr_release(ctx->gr);
     riptrm_big_release(ctx);
-    for (auto e : ctx->ev_pool) (void)hipEventDestroy(e);
+    for (auto& pool : ctx->ev_pool)
+      for (auto e : pool) (void)hipEventDestroy(e);
     for (auto e : {ctx->ev_fork, ctx->ev_join, ctx->ev_pass[0], ctx->ev_pass[1]})
       if (e) (void)hipEventDestroy(e);
     if (ctx->own_stream) (void)hipStreamDestroy(ctx->own_stream);
@@ -3148,7 +3199,8 @@ __global__ void k_list_range(DevParams P, int base, int count) {
 // and keeps the faster.  The two kernels add the same products in different fixed orders, so a
 // timing-based choice could make two runs of the same solve differ in the last bits; the default
 // (kind 1) therefore uses the fixed rule of spass_mode and never times anything.
-static int launch_gemv(riptrm_ctx* c, hipStream_t st, int list_in, int zero_cnt, int bound, int smode);
+static int launch_gemv(riptrm_ctx* c, hipStream_t st, int list_in, int zero_cnt, int bound, int smode,
+                       hipEvent_t* end_ev = nullptr);
 static DevParams params_for(const riptrm_ctx* c, int smode);
 
 // the persistent replicas' parameter block: the instances' parameters with the replica region's
@@ -3243,7 +3295,7 @@ static int persist_run(riptrm_ctx* c, int steps, int* n_active) {
       // (replicas only initialised), so the lock-step pipeline takes over from here
       c->persist_on = false;
       c->persist_fallbacks++;
-      c->ev_used -= (e0 ? 1 : 0) + (e1 ? 1 : 0);   // the unused events go back to the pool
+      c->ev_used[c->ev_cur] -= (e0 ? 1 : 0) + (e1 ? 1 : 0);   // the unused events go back to the pool
       reset_groups(c);
       HIPCHK(c, hipMemsetAsync(c->P.cnt, 0, 4 * sizeof(int32_t), c->stream));
       if (int rc = kick(c)) return rc;
@@ -3252,7 +3304,7 @@ static int persist_run(riptrm_ctx* c, int steps, int* n_active) {
     c->persist_launched = true;
     if (c->prof && e1) {
       HIPCHK(c, hipEventRecord(e1, c->stream));
-      c->ev_state.push_back({i0, i1});
+      c->ev_state[c->ev_cur].push_back({i0, i1});
     }
   }
   hipLaunchKernelGGL(k_persist_count, dim3(1), dim3(256), 0, c->stream, c->P, c->parity[0]);
@@ -3351,6 +3403,21 @@ int riptrm_nonnegpca_bind(riptrm_ctx* ctx, const double* S, int32_t n, int32_t b
     const char* ev = getenv("RIPTRM_SUP_DYNAMIC");
     P.sup_dyn = ev ? (atoi(ev) != 0) : 0;
   }
+  P.sup_perm = nullptr;
+  if (layout == RIPTRM_LAYOUT_SYMTILE) {
+    // static deal of k_spass_sup: index order u = g, g + G, ... unless RIPTRM_SUP_BALANCED=1 asks
+    // for the units largest first, dealt back and forth (riptrm_device.h).  The balanced deal gives
+    // every workgroup nearly the same bytes at any active count, yet measured 1-2.5% slower per
+    // launch at 32..56 active instances and equal at 64 (profiles/r7_spass_order_sweep.json), so
+    // it is opt-in
+    const char* ev = getenv("RIPTRM_SUP_BALANCED");
+    if (ev && atoi(ev) != 0) {
+      sup_perm_of(n, ctx->sup_perm);
+      HIPCHK(ctx, hipMemcpyAsync(ctx->ws + L.off_perm, ctx->sup_perm.data(), ctx->sup_perm.size() * sizeof(int32_t),
+                                 hipMemcpyHostToDevice, ctx->stream));
+      P.sup_perm = (const int32_t*)(ctx->ws + L.off_perm);
+    }
+  }
   P.clock_hz = ctx->clock_hz;
   P.outer_target = INT32_MAX;
   // persistent mode: the workspace has the replica region and every workgroup fits on its own CU
@@ -3420,7 +3487,8 @@ static DevParams params_for(const riptrm_ctx* c, int smode) {
   return P;
 }
 
-static int launch_gemv(riptrm_ctx* c, hipStream_t st, int list_in, int zero_cnt, int bound, int smode) {
+static int launch_gemv(riptrm_ctx* c, hipStream_t st, int list_in, int zero_cnt, int bound, int smode, hipEvent_t* end_ev) {
+  if (end_ev) *end_ev = nullptr;
   if (bound <= 0) return RIPTRM_OK;
   const bool sym = c->P.layout == RIPTRM_LAYOUT_SYMTILE;
   const int64_t blocks = (int64_t)bound * (sym ? c->P.ntiles : c->P.nrb);
@@ -3457,7 +3525,8 @@ static int launch_gemv(riptrm_ctx* c, hipStream_t st, int list_in, int zero_cnt,
   HIPCHK(c, hipGetLastError());
   if (c->prof && e1) {
     HIPCHK(c, hipEventRecord(e1, st));
-    c->ev_gemv.push_back({i0, i1});
+    c->ev_gemv[c->ev_cur].push_back({i0, i1});
+    if (end_ev) *end_ev = e1;
   }
   return RIPTRM_OK;
 }
@@ -3486,7 +3555,7 @@ static int launch_state(riptrm_ctx* c, hipStream_t st, int full, int list_in, in
   HIPCHK(c, hipGetLastError());
   if (c->prof && e1) {
     HIPCHK(c, hipEventRecord(e1, st));
-    c->ev_state.push_back({i0, i1});
+    c->ev_state[c->ev_cur].push_back({i0, i1});
   }
   return RIPTRM_OK;
 }
@@ -3547,7 +3616,9 @@ int riptrm_nonnegpca_operator_aw(riptrm_ctx* ctx, const double* x, const double*
 // `steps` lock-step iterations of every group.  Per step and group: S-pass then state kernel on
 // the group's stream.  The S-passes of the two groups are chained by events so they never run
 // concurrently (each gets the whole HBM; per-launch timing stays clean), while a group's state
-// kernel runs beside the other group's S-pass.
+// kernel runs beside the other group's S-pass.  The hand-over is one agent-scope event: the
+// finished pass's own end event when launches are timed, a marker recorded right behind the
+// launch when they are not (DESIGN.md section 5 has what each variant of the chain measured).
 constexpr int GRAPH_STEPS = 8;   // even: the ping-pong lists are back at the same parity
 
 // (re)capture GRAPH_STEPS lock-step iterations of group 0 on the private stream
@@ -3617,11 +3688,12 @@ static int run_steps(riptrm_ctx* c, int steps, int* n_active) {
       if (c->active_bound[g] <= 0) continue;  // nothing queued: keep the list (and its count 0)
       hipStream_t st = c->gstream[g];
       const int lin = g * 2 + c->parity[g], lout = g * 2 + (c->parity[g] ^ 1);
-      if (G == 2) HIPCHK(c, hipStreamWaitEvent(st, c->ev_pass[g ^ 1], 0));
+      // after the other group's pass: its end (timing) event when it has one, else the marker
+      if (G == 2) HIPCHK(c, hipStreamWaitEvent(st, c->pass_end[g ^ 1] ? c->pass_end[g ^ 1] : c->ev_pass[g ^ 1], 0));
       const int sm = spass_mode(c, c->active_bound[g]);
-      rc = launch_gemv(c, st, lin, lout, c->active_bound[g], sm);
+      rc = launch_gemv(c, st, lin, lout, c->active_bound[g], sm, &c->pass_end[g]);
       if (rc) return rc;
-      if (G == 2) HIPCHK(c, hipEventRecord(c->ev_pass[g], st));
+      if (G == 2 && !c->pass_end[g]) HIPCHK(c, hipEventRecord(c->ev_pass[g], st));
       rc = launch_state(c, st, 2, lin, lout, c->gsize[g], c->gbase[g], sm);
       if (rc) return rc;
       c->parity[g] ^= 1;
@@ -3633,8 +3705,12 @@ static int run_steps(riptrm_ctx* c, int steps, int* n_active) {
                              c->gstream[g]));
   rc = join_streams(c);
   if (rc) return rc;
+  // the previous chunk's pairs (all complete since its sync) are folded while this chunk runs
+  if (c->prof) prof_fold(c, c->ev_cur ^ 1);
   for (int g = 0; g < G; ++g) HIPCHK(c, hipStreamSynchronize(c->gstream[g]));
-  if (c->prof) prof_collect(c);
+  // everything recorded from here on goes with the next chunk, into the pool just folded
+  c->ev_cur ^= 1;
+  c->pass_end[0] = c->pass_end[1] = nullptr;
   for (int g = 0; g < G; ++g) c->active_bound[g] = h[g];
   if (n_active) *n_active = h[0] + (G == 2 ? h[1] : 0);
   return RIPTRM_OK;

@@ -68,6 +68,8 @@ SIGNATURES: Dict[str, tuple] = {
     "riptrm_nonnegpca_s_elems": (c_int64, [c_int32, c_int32]),
     "riptrm_workspace_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "riptrm_workspace_offset": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
+    "riptrm_sup_unit_bytes": (c_int64, [c_int32, c_int32]),
+    "riptrm_sup_deal": (c_int64, [c_int32, c_int32, c_int32, c_int32, P_int32, P_int32, P_int32, c_int64]),
     "riptrm_nonnegpca_pack": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
                                         c_int32, c_int64]),
     "riptrm_nonnegpca_bind": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
