@@ -412,7 +412,8 @@ int riptrm_si_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0
  * dim > RIPTRM_TRS_DIM_MAX: needs riptrm_trs_bind_workspace(order >= dim); up to `slots` subproblems
  * per pass on HBM-resident matrices (dim < RIPTRM_TRS_TRI_MIN: the hand-written eigensolver and SciPy's CG restated in
  * its eigen-coordinates; RIPTRM_TRS_TRI_MIN <= dim <= 1024: the cooperative tridiagonalisation T = H^T A H and the
- * subproblem in T's coordinates, riptrm_tri.h; above, or for a hard case, rocSOLVER
+ * subproblem in T's coordinates, riptrm_tri.h -- a hard case it hands back goes to the eigendecomposition
+ * path: the hand-written eigensolver (compact eigenvectors) at dim 150..199, rocSOLVER above; dim > 1024: rocSOLVER
  * dsyevd_strided_batched and SciPy's CG on A; the secular Newton per subproblem); synchronises.  A non-converged eigensolve fails the call
  * (RIPTRM_E_HIP naming the subproblem: scipy.linalg.eig raises there). */
 int riptrm_trs_gep(riptrm_ctx* ctx, int32_t dim, int32_t batch, const double* A, int64_t lda, int64_t a_stride,
@@ -425,8 +426,9 @@ int riptrm_trs_gep(riptrm_ctx* ctx, int32_t dim, int32_t batch, const double* A,
  * caller-owned device memory (256-byte aligned).  Each subproblem of a pass takes one slot; with
  * fewer slots than subproblems the pass repeats, with bitwise the same results.  Orders <= 149
  * take the hand-written eigensolver (riptrm_eig.h), 150..1024 the tridiagonal path (riptrm_tri.h, no
- * eigenvectors); rocSOLVER's dsyevd_strided_batched serves larger orders and the tridiagonal path's
- * hard cases, loaded at first use (dlopen of librocsolver.so.0; it manages its own workspace).  In a NonnegPCA solve an
+ * eigenvectors); a hard case that path hands back takes the eigendecomposition path: the hand-written
+ * eigensolver again at orders 150..199, rocSOLVER's dsyevd_strided_batched at 200..1024.  rocSOLVER also serves
+ * every order above 1024; it is loaded at first use (dlopen of librocsolver.so.0; it manages its own workspace).  In a NonnegPCA solve an
  * instance that reaches the subproblem (or, with the second-order test, a trial point) parks;
  * riptrm_solve_advance serves every parked instance in batched passes after its lock-step chunk and
  * synchronises then; an eigensolve that does not converge stops that instance (RIPTRM_ERR_EIGEN).

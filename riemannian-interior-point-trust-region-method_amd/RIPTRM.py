@@ -11,7 +11,8 @@ eqLagmult)`` whose ``log`` has the reference's columns, one row per inner iterat
   of HwCur lives in LDS (csrc/riptrm_trs.h), beyond that in HBM (csrc/riptrm_trs_big.hip), with the
   hand-written batched eigensolver (csrc/riptrm_eig.h) up to order 149, the hand-written
   distributed tridiagonalisation with the subproblem solved in T's coordinates (csrc/riptrm_tri.h)
-  for orders 150..1024, and rocSOLVER's dsyevd only for that path's hard cases and above 1024;
+  for orders 150..1024 (a hard case that path hands back is served by the hand-written eigensolver
+  at orders 150..199 and by rocSOLVER's dsyevd at 200..1024), and rocSOLVER's dsyevd above 1024;
 * the problem is a structured descriptor (``problems.NonnegPCAProblem``, ``si.SIProblem`` for
   StableIdentification or ``rosenbrock.RosenbrockProblem`` for Rosenbrock on Grassmann(n, k)) instead
   of a list of autograd closures, because closures cannot execute on the GPU;

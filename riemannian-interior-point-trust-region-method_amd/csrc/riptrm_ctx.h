@@ -1,6 +1,7 @@
 // riptrm_ctx.h — host-side context shared by the C-ABI translation units (internal).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <cstdlib>
 #include <string>
 #include <utility>
 #include <vector>
@@ -129,6 +130,13 @@ int riptrm_big_gep_ids(riptrm_ctx* c, int dim, const int32_t* sel, int count, co
 inline int fail(riptrm_ctx* c, int code, const std::string& msg) {
   if (c) c->err = msg;
   return code;
+}
+
+// the environment knob `name` is set and begins with v (read at every dispatch: tests flip knobs
+// between calls of one process)
+inline bool getenv_is(const char* name, char v) {
+  const char* e = getenv(name);
+  return e && e[0] == v;
 }
 
 #define HIPCHK(c, expr)                                                                    \

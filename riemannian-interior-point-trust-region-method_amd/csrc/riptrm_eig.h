@@ -279,7 +279,7 @@ __device__ __forceinline__ void gs_load(lds_t* X, const double* A, int64_t lda, 
 // k_refl_apply).  Scratch per matrix (two vectors of >= m doubles, k sc_stride apart): d at d0, e at
 // e0; the reflectors and tau (refl_doubles(m), layout refl_col / refl_tau) at R0 + k r_stride.
 // PH selects the phases one launch runs (bit 0 tridiagonalisation, 1 eigenvalues, 2 eigenvectors of T,
-// 3 orthogonality; 15: all, one workgroup per matrix).  The split launches (k_eig_split) run them as
+// 3 orthogonality; 15: all, one workgroup per matrix).  The split launches (launch_eig) run them as
 // four kernels so the eigenvalue and eigenvector phases spread over gridDim.y workgroups per matrix
 // (eigenvalues / vectors m y / Y .. m (y + 1) / Y of workgroup y): d and the split e travel through
 // the slot (d0, e0), the eigenvalues through ev, the vectors through A.

@@ -512,35 +512,20 @@ __device__ __forceinline__ void sup_flush(const DevParams& P, const double* outb
 
 // Unit order: a static deal (riptrm_device.h sup_deal_item / sup_item_unit: the units largest first
 // and dealt back and forth, so every workgroup gets nearly the same bytes at any active count; or,
-// without P.sup_perm, in index order u = g, g + G, ...) or, with P.sup_dyn, tickets from a per-list counter
-// (cnt[8 + list_in]): a workgroup takes its next unit when it finishes one, so CUs that also run
-// the other group's state kernel, and units of 3 vs 4 tiles or two right-hand sides, no longer
-// decide the launch's end.  The next ticket is fetched at the start of the current unit (its
-// latency overlaps the unit's first loads); the last workgroup to finish resets the counter for
-// the next launch.  Every unit writes its fixed slots, so results do not depend on the order.
+// without P.sup_perm, in index order u = g, g + G, ...).  Every unit writes its fixed slots, so results
+// do not depend on the order.
 __global__ void __launch_bounds__(SP_THREADS, 1) k_spass_sup(DevParams P, int list_in, int zero_cnt) {
   static_assert(SP_THREADS == 2 * SW, "sup_flush: one thread per element of the two sides");
   __shared__ double red[2][SP_WAVES][SW];
   __shared__ double outb[SUP_OCAP];
   __shared__ int meta[SUP_MAXU][2];
-  __shared__ int tick_next;
   if (zero_cnt >= 0 && blockIdx.x == 0 && threadIdx.x == 0) P.cnt[zero_cnt] = 0;
   const int nact = P.cnt[list_in];
   const int total = nact * P.nsup;
   int used = 0, nslot = 0, rsel = 0;
-  const bool dyn = P.sup_dyn != 0;
-  unsigned int* tick = (unsigned int*)P.cnt + 8 + list_in;
-  unsigned int* done = (unsigned int*)P.cnt + 12 + list_in;
-  const int32_t* perm = dyn ? nullptr : P.sup_perm;   // tickets hand the units out in index order
+  const int32_t* perm = P.sup_perm;
   int q = blockIdx.x, round = 0;   // item of the launch (the static deal's round 0 is item g)
-  if (dyn) {
-    if (threadIdx.x == 0) tick_next = (int)atomicAdd(tick, 1u);
-    __syncthreads();
-    q = tick_next;
-  }
   while (q < total) {
-    unsigned int pre = 0;
-    if (dyn && threadIdx.x == 0) pre = atomicAdd(tick, 1u);   // next unit, in flight during this one
     int slot, unit;
     sup_item_unit(q, nact, P.nsup, perm, slot, unit);
     const int u = slot * P.nsup + unit;   // what sup_flush decodes
@@ -565,23 +550,9 @@ __global__ void __launch_bounds__(SP_THREADS, 1) k_spass_sup(DevParams P, int li
     }
     used += nr * 2 * SW;
     ++nslot;
-    if (dyn) {
-      __syncthreads();                 // every thread has read tick_next (and meta is ordered)
-      if (threadIdx.x == 0) tick_next = (int)pre;
-      __syncthreads();
-      q = tick_next;
-    } else {
-      q = sup_deal_item(++round, (int)blockIdx.x, (int)gridDim.x, perm != nullptr);
-    }
+    q = sup_deal_item(++round, (int)blockIdx.x, (int)gridDim.x, perm != nullptr);
   }
   if (nslot > 0) sup_flush(P, outb, meta, nslot, list_in);
-  if (dyn && threadIdx.x == 0) {
-    // every workgroup has drawn its last ticket before it counts itself done: the last one resets
-    if (atomicAdd(done, 1u) == gridDim.x - 1) {
-      atomicExch(tick, 0u);
-      atomicExch(done, 0u);
-    }
-  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3399,10 +3370,6 @@ int riptrm_nonnegpca_bind(riptrm_ctx* ctx, const double* S, int32_t n, int32_t b
   P.req = (int32_t*)(ctx->ws + L.off_req);
   P.cnt = (int32_t*)(ctx->ws + L.off_cnt);
   P.pbatch = batch;
-  {   // S-pass unit order (k_spass_sup): RIPTRM_SUP_DYNAMIC=0 / 1 overrides the default
-    const char* ev = getenv("RIPTRM_SUP_DYNAMIC");
-    P.sup_dyn = ev ? (atoi(ev) != 0) : 0;
-  }
   P.sup_perm = nullptr;
   if (layout == RIPTRM_LAYOUT_SYMTILE) {
     // static deal of k_spass_sup: index order u = g, g + G, ... unless RIPTRM_SUP_BALANCED=1 asks
@@ -3798,10 +3765,8 @@ int riptrm_solve_begin(riptrm_ctx* ctx, const riptrm_options* opt, const double*
     return fail(ctx, RIPTRM_E_ARG, "solve_begin: unknown trs_solver");
   if (opt->trs_solver == RIPTRM_TRS_SOLVER_EXACT_REPMAT && ctx->P.n < 2)
     return fail(ctx, RIPTRM_E_ARG, "solve_begin: Exact_RepMat needs n >= 2");
-  {   // A/B: the HBM subproblem path below its size limit too (comparisons with the LDS solver)
-    const char* e = getenv("RIPTRM_TRS_HBM");
-    ctx->P.trs_hbm = (e && e[0] == '1') ? 1 : 0;
-  }
+  // A/B: the HBM subproblem path below its size limit too (comparisons with the LDS solver)
+  ctx->P.trs_hbm = getenv_is("RIPTRM_TRS_HBM", '1') ? 1 : 0;
   if (opt->trs_solver == RIPTRM_TRS_SOLVER_EXACT_REPMAT && big_trs_path(ctx) &&
       (!ctx->big_ws || ctx->big_order < ctx->P.n || ctx->big_slots < 1))
     return fail(ctx, RIPTRM_E_STATE, "solve_begin: Exact_RepMat above RIPTRM_TRS_DIM_MAX + 1 needs "

@@ -1802,8 +1802,7 @@ static int si_repmat_d(riptrm_ctx* c, const SIParams& P, int ids_off, int cnt, i
     HIPCHK(c, hipFuncSetAttribute((const void*)k_si_repmat<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   // prepare / frame once per instance (k_si_prep), then the tdim column workgroups on its records;
   // RIPTRM_SI_PREP=0: every workgroup recomputes them (A/B; the same values)
-  const char* pe = getenv("RIPTRM_SI_PREP");
-  const int pre = (pe && pe[0] == '0') ? 0 : 1;
+  const int pre = getenv_is("RIPTRM_SI_PREP", '0') ? 0 : 1;
   if (pre) {
     if (shm > 64 * 1024)
       HIPCHK(c, hipFuncSetAttribute((const void*)k_si_prep<D>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
@@ -1967,8 +1966,7 @@ int riptrm_si_solve(riptrm_ctx* ctx, const riptrm_options* opt, const double* x0
   const int B = ctx->si->batch;
   std::vector<double> st((size_t)B * RIPTRM_STAT_NFIELDS);
   P.mode = MODE_RESUME;
-  const char* ce = getenv("RIPTRM_SI_CACHE");
-  const bool cache = P.trsC && ce && ce[0] == '1' && riptrm_big_kcache_usable(tdim);
+  const bool cache = P.trsC && getenv_is("RIPTRM_SI_CACHE", '1') && riptrm_big_kcache_usable(tdim);
   KeyedEigCache kc;
   kc.keys = P.trsP;
   kc.kstride = kc.klen = 3 * d * d + ctx->si->prob.m + 1;

@@ -20,7 +20,8 @@
 //      pass's tag bit (a rounding-level change every workgroup sees alike), polled with sc1 loads
 //      (MI355X_MICROARCH.md, persistent hand-offs), two parities, plus one arrival granule {value,
 //      check, pass} per workgroup and pass so no workgroup overwrites a parity another still reads.
-//   2. k_refl_big: b = H^T a (and x = H y at the end) with the reflectors from HBM, one wave.
+//   2. k_refl_gram + k_refl_blk: b = H^T a (and x = H y at the end), 16 reflections per round in the
+//      compact WY form, one 512-thread workgroup per matrix.
 //   3. k_tri_solve: the extreme eigenvalues of T by Sturm bisection (riptrm_eig.h's counts), the
 //      hard-case test on lam_min's eigenvector (a twisted factorisation), the secular Newton of
 //      k_secular with (T + lam I)^-1 applied by LDL^T solves instead of an eigenbasis, and SciPy's CG
@@ -48,37 +49,36 @@ constexpr int TRI_MAX = RIPTRM_TRS_TRI_MAX;      // (EL = 32 for 2048 spilled th
 static_assert(TRI_MIN > 64 && TRI_MIN <= riptrm_eig::EIG_LDS_MAX + 1 && TRI_MAX == 1024, "riptrm_tri: orders");
 constexpr unsigned long long TRI_TIMEOUT = 200000000ull;   // 2 s of the 100 MHz wall clock
 
-// elements per lane (EL) and rows per wave (RW) of order m: 32 doubles of the matrix per lane
+// elements per lane (EL) and rows per wave (RW = 32 / EL) of order m: 32 doubles of the matrix per lane
 __host__ __device__ constexpr int tri_el(int m) { return m <= 256 ? 4 : (m <= 512 ? 8 : 16); }
 __host__ __device__ constexpr int tri_rw(int m) { return 32 / tri_el(m); }
 __host__ __device__ constexpr int tri_groups(int m) { return (m + 8 * tri_rw(m) - 1) / (8 * tri_rw(m)); }
 // granules per matrix: 2 parities x [{p, column}: m][arrivals: G]
 __host__ __device__ constexpr int64_t tri_par(int m) { return (int64_t)m + tri_groups(m); }
 __host__ __device__ constexpr int64_t tri_granules(int m) { return 2 * tri_par(m); }
-// byte offset of granule g: eight granules (one 128-byte line) every 128 << sp bytes (sp = 0: packed;
-// larger sp spreads the lines every workgroup polls over more memory channels)
-__host__ __device__ constexpr int64_t gran_off(int64_t g, int sp) { return ((g >> 3) << (7 + sp)) + ((g & 7) << 4); }
-__host__ __device__ constexpr int64_t tri_grid_bytes(int64_t granules, int sp) { return ((granules + 7) >> 3) << (7 + sp); }
+// byte offset of granule g: packed, eight granules per 128-byte line
+__host__ __device__ constexpr int64_t gran_off(int64_t g) { return g << 4; }
+__host__ __device__ constexpr int64_t tri_grid_bytes(int64_t granules) { return ((granules + 7) >> 3) << 7; }
 
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 __device__ __forceinline__ unsigned tag_check(unsigned lo, unsigned hi, unsigned pass) {
   return lo ^ hi ^ (pass * 0x9E3779B9u);
 }
-__device__ __forceinline__ void st_gran(__amdgpu_buffer_rsrc_t rs, int64_t g, int sp, double v, unsigned pass) {
+__device__ __forceinline__ void st_gran(__amdgpu_buffer_rsrc_t rs, int64_t g, double v, unsigned pass) {
   const unsigned lo = (unsigned)__double2loint(v), hi = (unsigned)__double2hiint(v);
   const u32x4 q = {lo, hi, tag_check(lo, hi, pass), pass};
-  __builtin_amdgcn_raw_buffer_store_b128(q, rs, (int)gran_off(g, sp), 0, 16);   // aux 16: sc1 (write-through)
+  __builtin_amdgcn_raw_buffer_store_b128(q, rs, (int)gran_off(g), 0, 16);   // aux 16: sc1 (write-through)
 }
 
 // the pair granule {a, b} of pass `pass`: both mantissas' last bits = the pass's tag bit, which
 // alternates between the passes sharing a parity (and is 1 on each parity's first pass: the grid
 // starts zeroed); a reader takes it when both bits match (a granule torn between passes mixes them)
 __device__ __forceinline__ unsigned pair_bit(unsigned pass) { return ((pass + 1) >> 1) & 1u; }
-__device__ __forceinline__ void st_pair(__amdgpu_buffer_rsrc_t rs, int64_t g, int sp, double a, double b, unsigned pass) {
+__device__ __forceinline__ void st_pair(__amdgpu_buffer_rsrc_t rs, int64_t g, double a, double b, unsigned pass) {
   const unsigned t = pair_bit(pass);
   const u32x4 q = {((unsigned)__double2loint(a) & ~1u) | t, (unsigned)__double2hiint(a),
                    ((unsigned)__double2loint(b) & ~1u) | t, (unsigned)__double2hiint(b)};
-  __builtin_amdgcn_raw_buffer_store_b128(q, rs, (int)gran_off(g, sp), 0, 16);   // aux 16: sc1 (write-through)
+  __builtin_amdgcn_raw_buffer_store_b128(q, rs, (int)gran_off(g), 0, 16);   // aux 16: sc1 (write-through)
 }
 
 struct TriArgs {
@@ -93,8 +93,6 @@ struct TriArgs {
   void* grid;            // granules, tri_granules(m) per launch slot (zeroed before the launch)
   int64_t grid_bytes;
   int m, G;
-  int sleep;             // s_sleep 1 rounds between polls (RIPTRM_TRI_SLEEP; default 1)
-  int spread;            // gran_off's sp (RIPTRM_TRI_SPREAD)
   long long* hops;       // diagnostics (RIPTRM_TRI_STAMPS=2): matrix 0, every workgroup, steps i = 16 s: the
                          // wall clock (100 MHz, chip-wide) at [g][s][0] its gather's start, [1] its end
   long long* stamps;     // diagnostics (RIPTRM_TRI_STAMPS=1): workgroup 0 of matrix 0 accumulates clock64
@@ -138,8 +136,9 @@ __device__ __forceinline__ void bar_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n
 // dsytd2 (lower) of the m x m matrix of slot k0 + blockIdx.y on gridDim.x = G workgroups: d, e, the
 // reflectors and tau into the slot.  Row l lives on workgroup l mod G, wave (l / G) mod 8, register
 // row (l / G) / 8, lane j mod 64 holding columns j = lane + 64 q.
-template <int EL, int RW>
+template <int EL>
 __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
+  constexpr int RW = 32 / EL;
   __shared__ double Vbuf[2][EL * 64];   // v_i and v_{i+1} (by step parity)
   __shared__ double GP[EL * 64];        // gathered p (written by the gather, read by the column step)
   __shared__ double W[EL * 64];         // w = p + a2 v (column step -> every wave's update)
@@ -160,7 +159,6 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
   const bool writer = g == (m - 1) % G;   // owns row m - 1, active to the last step: writes d, e, H
   const __amdgpu_buffer_rsrc_t rs = __builtin_amdgcn_make_buffer_rsrc(a.grid, 0, (int)a.grid_bytes, 0x00020000);
   const int64_t gbase = (int64_t)ks * tri_granules(m);
-  const int gsp = a.spread;
   const int64_t par = tri_par(m);
 
   // own rows into registers (unconditional loads of clamped addresses)
@@ -218,10 +216,10 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
 #pragma unroll
         for (int q = 0; q < EL; ++q) acc += (lane + 64 * q >= 1) ? Ar[s][q] * vq[q] : 0.0;
         const double p = tau_c * riptrm_wave::wave_sum(acc);
-        if (lane == 1) st_pair(rs, pb + l, gsp, p, Ar[s][0], 1u);
+        if (lane == 1) st_pair(rs, pb + l, p, Ar[s][0], 1u);
       }
     }
-    if (tid == 0) st_gran(rs, pb + m + g, gsp, 0.0, 1u);
+    if (tid == 0) st_gran(rs, pb + m + g, 0.0, 1u);
   }
 
   constexpr int NG = (64 * EL + 64 + TT - 1) / TT;   // granules polled per thread (upper bound)
@@ -258,7 +256,7 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
         u32x4 qv[NG];
 #pragma unroll
         for (int u = 0; u < NG; ++u)
-          if (pend & (1 << u)) qv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)gran_off(gi[u], gsp), 0, 16);
+          if (pend & (1 << u)) qv[u] = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)gran_off(gi[u]), 0, 16);
 #pragma unroll
         for (int u = 0; u < NG; ++u)
           if (pend & (1 << u)) {
@@ -280,7 +278,7 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
           failed = true;
           break;
         }
-        for (int z = 0; z < a.sleep; ++z) __builtin_amdgcn_s_sleep(1);
+        __builtin_amdgcn_s_sleep(1);
       }
       sp = riptrm_wave::wave_sum(sp);
       if (lane == 0) red[0][w] = sp;
@@ -300,7 +298,7 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
     // this workgroup has read pass i + 1: the parity of pass i + 2 (= pass i's) may be reused
     const int64_t pn = gbase + (int64_t)((pass + 1) & 1) * par;
     const bool more = i + 1 <= m - 2;
-    if (tid == 0 && more) st_gran(rs, pn + m + g, gsp, 0.0, pass + 1);
+    if (tid == 0 && more) st_gran(rs, pn + m + g, 0.0, pass + 1);
     // The column step, spread over the eight waves (wave w owns the columns j = lane + 64 q, q = w + 8 t):
     // w = p + a2 v with a2 = -tau (p . v) / 2, the column i + 1 of the updated matrix, its reflector.
     // Two block sums (p . v, its wave partials made in the gather, and the reflector's sum of squares:
@@ -410,7 +408,7 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
         double ac = Ar[s][0];
 #pragma unroll
         for (int q = 1; q < EL; ++q) ac = q == qc ? Ar[s][q] : ac;
-        if (lane == ((i + 2) & 63)) st_pair(rs, pn + l, gsp, p, ac, pass + 1);
+        if (lane == ((i + 2) & 63)) st_pair(rs, pn + l, p, ac, pass + 1);
       }
     }
     tau_c = tau_n;
@@ -427,106 +425,6 @@ __global__ void __launch_bounds__(TT) k_tridiag_dist(TriArgs a) {
     stp[4] = sa;
     stp[5] = sb;
     stp[6] = sc;
-  }
-}
-
-// After k_tridiag_dist for the hand-written eigensolver's later phases (riptrm_eig.h k_eig_lds with
-// PH & 1 == 0, which read d and the SPLIT e): e_j -> 0 where |e_j| <= 4 eps ||T|| (phase 1's split),
-// and a non-finite T marks info = 1 with NaN eigenvalues (phase 1's non-finite input test).  One
-// workgroup of 256 threads per matrix.
-__global__ void __launch_bounds__(256) k_tri_split(double* d0, double* e0, int64_t de_stride, int m, int32_t* infos,
-                                                   double* ev0, int64_t ev_stride) {
-  __shared__ double red[4];
-  __shared__ int badw;
-  const int k = blockIdx.x, tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const double* d = d0 + (int64_t)k * de_stride;
-  double* e = e0 + (int64_t)k * de_stride;
-  if (tid == 0) badw = 0;
-  double tn0 = 0.0;
-  int bad = 0;
-  for (int j = tid; j < m; j += 256) {
-    const double ej = j < m - 1 ? e[j] : 0.0, ep = j > 0 ? e[j - 1] : 0.0;
-    bad |= !isfinite(d[j]) | !isfinite(ej);
-    tn0 = fmax(tn0, fabs(d[j]) + fabs(ep) + fabs(ej));
-  }
-  tn0 = riptrm_wave::wave_max(tn0);
-  if (lane == 0) red[w] = tn0;
-  __syncthreads();
-  if (bad) badw = 1;
-  tn0 = fmax(fmax(red[0], red[1]), fmax(red[2], red[3]));
-  __syncthreads();
-  if (badw || infos[k] != 0) {
-    if (tid == 0 && infos[k] == 0) infos[k] = 1;
-    for (int j = tid; j < m; j += 256) ev0[(int64_t)k * ev_stride + j] = NAN;
-    return;
-  }
-  for (int j = tid; j < m - 1; j += 256)
-    if (fabs(e[j]) <= 4.0 * DBL_EPSILON * tn0) e[j] = 0.0;
-}
-
-// v <- H^T v (backward = 0: H_{m-2} ... H_0 v) or H v (backward = 1), H the reflectors of slot k0 +
-// blockIdx.y at r_off (riptrm_eig layout), from slot offset voff to ooff; one wave, lane l holding
-// elements l + 64 q (the k_refl_apply arithmetic).  The reflectors stream from HBM / L2 through a ring
-// of RD register sets: reflector t + RD is requested while t is applied (one reflection is ~0.2 us
-// of arithmetic against ~1-2 us of load latency).
-template <int EL>
-__global__ void __launch_bounds__(64) k_refl_big(double* base, int64_t sd, int k0, int m, int64_t r_off, int64_t voff,
-                                                 int64_t ooff, int backward) {
-  constexpr int RD = EL <= 8 ? 8 : 4;   // ring depth (EL = 16: 4 x 16 doubles in flight per lane)
-  double* sb = base + (int64_t)(k0 + blockIdx.y) * sd;
-  const double* R = sb + r_off;
-  const int lane = threadIdx.x;
-  double v[EL];
-#pragma unroll
-  for (int q = 0; q < EL; ++q) {
-    const int j = lane + 64 * q;
-    v[q] = j < m ? sb[voff + j] : 0.0;
-  }
-  const int nt = riptrm_eig::refl_tau(m), nr = m - 1;
-  double ring[RD][EL], rtau[RD];
-  auto fetch = [&](int t, double (&u)[EL], double& tau) {
-    const int i = backward ? m - 2 - t : t;
-    const bool live = t < nr;
-    tau = R[live ? nt + i : nt];
-    const int c = riptrm_eig::refl_col(m, i) - i - 1;
-#pragma unroll
-    for (int q = 0; q < EL; ++q) {
-      const int j = lane + 64 * q;
-      const bool ok = live && j > i && j < m;
-      u[q] = R[ok ? c + j : nt];
-    }
-  };
-#pragma unroll
-  for (int r = 0; r < RD; ++r) fetch(r, ring[r], rtau[r]);
-  for (int t0 = 0; t0 < nr; t0 += RD) {
-#pragma unroll
-    for (int r = 0; r < RD; ++r) {
-      const int t = t0 + r;
-      if (t < nr) {   // uniform
-        const int i = backward ? m - 2 - t : t;
-        double u[EL];
-#pragma unroll
-        for (int q = 0; q < EL; ++q) {
-          const int j = lane + 64 * q;
-          u[q] = (j > i && j < m) ? ring[r][q] : 0.0;
-        }
-        const double tau = rtau[r];
-        fetch(t + RD, ring[r], rtau[r]);   // the slot is free: request reflector t + RD
-        if (tau != 0.0) {   // uniform
-          double s = 0.0;
-#pragma unroll
-          for (int q = 0; q < EL; ++q) s += u[q] * v[q];
-          const double f = tau * riptrm_wave::wave_sum(s);
-#pragma unroll
-          for (int q = 0; q < EL; ++q) v[q] = v[q] - f * u[q];
-        }
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < EL; ++q) {
-    const int j = lane + 64 * q;
-    if (j < m) sb[ooff + j] = v[q];
   }
 }
 
@@ -1441,54 +1339,6 @@ __global__ void __launch_bounds__(256) k_tri_solve(double* base, int64_t sd, int
   }
 }
 
-// v <- H^T v (backward = 0: H_{m-2} ... H_0 v) or H v (backward = 1) for orders up to 1024 on one
-// 1024-thread workgroup (element j on thread j): per reflection each wave's share of the dot product,
-// one workgroup barrier, the 16 wave partials added in a fixed order (two parities of the partial
-// buffer, so a wave may run one reflection ahead); reflector t + 8 is requested while t is applied.
-// ~0.1 us per reflection where one wave with the vector in registers waited on the reflectors' loads.
-__global__ void __launch_bounds__(1024) k_refl_wg(double* base, int64_t sd, int k0, int m, int64_t r_off, int64_t voff,
-                                                  int64_t ooff, int backward) {
-  constexpr int RD = 8;
-  __shared__ double red[2][16];
-  double* sb = base + (int64_t)(k0 + blockIdx.y) * sd;
-  const double* R = sb + r_off;
-  const int j = threadIdx.x, lane = j & 63, w = j >> 6;
-  double v = j < m ? sb[voff + j] : 0.0;
-  const int nt = riptrm_eig::refl_tau(m), nr = m - 1;
-  double ring[RD], rtau[RD];
-  auto fetch = [&](int t, double& u, double& tau) {
-    const int i = backward ? m - 2 - t : t;
-    const bool live = t < nr;
-    tau = R[live ? nt + i : nt];
-    const bool ok = live && j > i && j < m;
-    u = R[ok ? riptrm_eig::refl_col(m, i) - i - 1 + j : nt];
-  };
-#pragma unroll
-  for (int r = 0; r < RD; ++r) fetch(r, ring[r], rtau[r]);
-  for (int t0 = 0; t0 < nr; t0 += RD) {
-#pragma unroll
-    for (int r = 0; r < RD; ++r) {
-      const int t = t0 + r;
-      if (t < nr) {   // uniform
-        const int i = backward ? m - 2 - t : t;
-        const double u = (j > i && j < m) ? ring[r] : 0.0;
-        const double tau = rtau[r];
-        fetch(t + RD, ring[r], rtau[r]);
-        if (tau != 0.0) {   // uniform
-          const double s = riptrm_wave::wave_sum(u * v);
-          if (lane == 0) red[t & 1][w] = s;
-          __syncthreads();
-          double S = 0.0;
-#pragma unroll
-          for (int q = 0; q < 16; ++q) S += red[t & 1][q];
-          v = v - (tau * S) * u;
-        }
-      }
-    }
-  }
-  if (j < m) sb[ooff + j] = v;
-}
-
 // ---- blocked reflector application ----------------------------------------------------------------
 // RB consecutive reflections H_a = I - tau_a u_a u_a^T (a = 0 .. RB - 1) compose to H_0 ... H_{RB-1} =
 // I - U T U^T with T upper triangular (the compact WY form, LAPACK dlarft's forward columnwise recurrence:
@@ -1598,8 +1448,8 @@ __global__ void __launch_bounds__(256) k_refl_gram(double* base, int64_t sd, int
 // 5.8k cycles per round and insensitive to bytes and to where they come from -- reading only live lines
 // (no change) and 1, 2 or 4 L2-prefetch workgroups on workgroup 0's XCD (no change) -- so the floor is
 // the CU's own vector-memory return path (32 x 512 B per wave per round) and the reduction's issue.
-// E elements per thread (1024 / E threads): E = 2 the default, E = 1 four waves per SIMD (A/B,
-// RIPTRM_TRI_REFL_E=1)
+// E elements per thread (1024 / E threads): E = 2 is the one in use (E = 1, four waves per SIMD, measured
+// no faster)
 template <int E>
 __global__ void __launch_bounds__(1024 / E) k_refl_blk(double* base, int64_t sd, int k0, int m, int64_t r_off, int64_t goff,
                                                   int64_t voff, int64_t ooff, int backward, long long* stamps) {

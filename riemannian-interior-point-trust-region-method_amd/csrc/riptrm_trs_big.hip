@@ -67,7 +67,8 @@ constexpr int NVS = 12;        // vectors per slot
 enum Vs : int { VS_W = 0, VS_U, VS_A, VS_CGX, VS_R, VS_P, VS_Q, VS_EV, VS_EW, VS_G, VS_PE, VS_X };
 
 // one slot for matrices of order N: [N x N][NVS vectors of vpad(N)][NSC scalars]; after the slots:
-// int32 info[slots], ids[slots], flag[8], sweeps[slots], hits[slots] (+ pad), double residual[slots]
+// int32 info[slots], ids[slots], flag[8], [slots: unused], hits[slots] (+ pad), double [slots: unused]
+// (the two unused arrays were the retired Jacobi variants' scratch; the layout and size stay)
 // ... then [the eigensolver's reflectors: riptrm_eig::refl_doubles(N)] (orders it serves)
 // (every order m <= N the hand-written eigensolver or the tridiagonal path serves: N <= TRI_MAX)
 __host__ __device__ inline int64_t refl_of(int64_t N) {
@@ -350,8 +351,6 @@ __device__ __forceinline__ void wg_matvec(const double* __restrict__ A, int64_t 
 // per-iteration mat-vec latency is what counts there)
 constexpr int CG_LDS_BYTES = 124 * 1024;
 inline int cg_lds_rows(int m) {
-  const char* e = getenv("RIPTRM_CG_LDS");   // "0": stream every row (A/B measurements)
-  if (e && e[0] == '0') return 0;
   const int r = std::min(m, CG_LDS_BYTES / (8 * m));
   return r >= m ? m : r / 4 * 4;
 }
@@ -1303,11 +1302,7 @@ typedef int (*fn_create_t)(void**);
 typedef int (*fn_set_stream_t)(void*, hipStream_t);
 typedef int (*fn_destroy_t)(void*);
 typedef int (*fn_syevd_sb_t)(void*, int, int, int, double*, int, int64_t, double*, int64_t, double*, int64_t, int*, int);
-typedef int (*fn_syevj_sb_t)(void*, int, int, int, int, double*, int, int64_t, double, double*, int, int*, double*, int64_t,
-                             int*, int);
-typedef int (*fn_syevdj_sb_t)(void*, int, int, int, double*, int, int64_t, double*, int64_t, int*, int);
-typedef int (*fn_syevd_t)(void*, int, int, int, double*, int, double*, double*, int*);
-constexpr int EVECT_ORIGINAL = 211, EVECT_NONE = 213, FILL_UPPER = 121, ESORT_ASCENDING = 252;
+constexpr int EVECT_ORIGINAL = 211, EVECT_NONE = 213, FILL_UPPER = 121;
 
 struct Solver {
   bool tried = false, ok = false;
@@ -1316,9 +1311,6 @@ struct Solver {
   fn_set_stream_t set_stream = nullptr;
   fn_destroy_t destroy = nullptr;
   fn_syevd_sb_t syevd_sb = nullptr;
-  fn_syevj_sb_t syevj_sb = nullptr;     // A/B only (RIPTRM_BIG_EIG)
-  fn_syevdj_sb_t syevdj_sb = nullptr;
-  fn_syevd_t syevd = nullptr;           // one matrix per call (large orders)
 };
 
 static Solver& solver() {
@@ -1347,9 +1339,6 @@ static Solver& solver() {
   s.set_stream = (fn_set_stream_t)dlsym(blas, "rocblas_set_stream");
   s.destroy = (fn_destroy_t)dlsym(blas, "rocblas_destroy_handle");
   s.syevd_sb = (fn_syevd_sb_t)dlsym(sol, "rocsolver_dsyevd_strided_batched");
-  s.syevj_sb = (fn_syevj_sb_t)dlsym(sol, "rocsolver_dsyevj_strided_batched");
-  s.syevdj_sb = (fn_syevdj_sb_t)dlsym(sol, "rocsolver_dsyevdj_strided_batched");
-  s.syevd = (fn_syevd_t)dlsym(sol, "rocsolver_dsyevd");
   s.ok = s.create && s.set_stream && s.destroy && s.syevd_sb;
   if (!s.ok)
     s.why = "rocBLAS / rocSOLVER lack rocblas_create_handle / rocblas_set_stream / rocsolver_dsyevd_strided_batched";
@@ -1361,9 +1350,12 @@ static Solver& solver() {
 using namespace riptrm_big;
 
 static unsigned blocks_of(int64_t n, int per) { return (unsigned)((n + per - 1) / per); }
-static bool getenv_is(const char* name, char v) {
-  const char* e = getenv(name);
-  return e && e[0] == v;
+
+// RIPTRM_BIG_EIG: unset or 'h...' the default routing (the hand-written eigensolver up to EIG_LDS_MAX, the
+// tridiagonal path from TRI_MIN to TRI_MAX); anything else rocSOLVER's batched dsyevd at every order
+static bool eig_default_routing() {
+  const char* e = getenv("RIPTRM_BIG_EIG");
+  return !e || e[0] == 'h';
 }
 
 static int big_handle(riptrm_ctx* c) {
@@ -1406,16 +1398,9 @@ static Bat bat_of(riptrm_ctx* c) {
 static int32_t* tail_of(riptrm_ctx* c) { return (int32_t*)((double*)c->big_ws + slot_doubles(c->big_order) * c->big_slots); }
 static int32_t* flag_of(riptrm_ctx* c) { return tail_of(c) + 2 * c->big_slots; }
 
-// A = Q diag(lam) Q^T for the pass's cnt slots (A at slot offset aoff, lda; eigenvalues ascending into
-// VS_EV, eigenvectors over A when vectors): rocSOLVER dsyevd (default) or, for A/B measurements
-// (RIPTRM_BIG_EIG=j / dj), its Jacobi dsyevj / dsyevdj
-// the hand-written eigensolver serves order m (riptrm_eig.h; RIPTRM_BIG_EIG=r, or j / dj / s, keeps
-// rocSOLVER for A/B measurements): its eigenvectors are compact (those of the tridiagonal form over
-// the matrix, the reflectors in the slot), applied through k_refl_apply
-static bool eig_compact(int m) {
-  const char* e = getenv("RIPTRM_BIG_EIG");
-  return m <= riptrm_eig::EIG_LDS_MAX && !(e && e[0] != 'h');
-}
+// the hand-written eigensolver serves order m (riptrm_eig.h): its eigenvectors are compact (those of the
+// tridiagonal form over the matrix, the reflectors in the slot), applied through k_refl_apply
+static bool eig_compact(int m) { return m <= riptrm_eig::EIG_LDS_MAX && eig_default_routing(); }
 
 static int refl_apply(riptrm_ctx* c, const Bat& B, int cnt, int m, int64_t voff, int64_t ooff, int backward) {
   const size_t shm = (size_t)(riptrm_eig::refl_tau(m) + m) * sizeof(double);
@@ -1425,54 +1410,27 @@ static int refl_apply(riptrm_ctx* c, const Bat& B, int cnt, int m, int64_t voff,
   return RIPTRM_OK;
 }
 
-// the distributed tridiagonalisation (riptrm_tri.h) for the hand-written eigensolver's first phase:
-// RIPTRM_EIG_TRI=1 (A/B; orders >= 64)
-static int tri_launch(riptrm_ctx* c, const riptrm_tri::TriArgs& a, int cnt, int m);
-static bool eig_tri_front(int m) {
-  const char* e = getenv("RIPTRM_EIG_TRI");
-  return m >= 64 && e && e[0] == '1';
-}
-
-// k_eig_lds with 1024 threads per matrix (16 waves: the symv and rank-2 update of the
-// tridiagonalisation hide more LDS latency), or 512 (RIPTRM_EIG_THREADS=512, A/B)
+// k_eig_lds with 1024 threads per matrix for the tridiagonalisation and the orthogonality pass (16 waves:
+// the symv and rank-2 update hide more LDS latency).  With stamps (RIPTRM_EIG_STAMPS), one launch of
+// all four phases that records their clocks.
 static int launch_eig(riptrm_ctx* c, int cnt, int m, double* A, int64_t a_stride, int lda, double* ev, int64_t ev_stride,
                       double* d, double* e, int64_t sc_stride, double* R, int64_t r_stride, int32_t* infos, int vectors,
                       long long* stamps) {
   const size_t shm = riptrm_eig::eig_lds_bytes(m);
-  const char* t = getenv("RIPTRM_EIG_THREADS");
-  const char* sp = getenv("RIPTRM_EIG_SPLIT");
-  if (!stamps && !(sp && sp[0] == '0') && !(t && atoi(t) == 512)) {
+  if (!stamps) {
     // four launches: the tridiagonalisation (one workgroup per matrix), the eigenvalues and the
     // vectors of T over ~50 indices per workgroup (four per matrix at m = 199: the whole chip for a
     // batch of 64), the orthogonality pass (one per matrix).  The same arithmetic as one launch.
     const int yv = (m + 49) / 50;
-    if (eig_tri_front(m)) {   // T across the chip, then phase 1's split / non-finite test
-      riptrm_tri::TriArgs ta{};
-      ta.A0 = A;
-      ta.a_stride = a_stride;
-      ta.lda = lda;
-      ta.d0 = d;
-      ta.e0 = e;
-      ta.de_stride = sc_stride;
-      ta.R0 = R;
-      ta.r_stride = r_stride;
-      ta.infos = infos;
-      if (int rc = tri_launch(c, ta, cnt, m)) return rc;
-      hipLaunchKernelGGL(riptrm_tri::k_tri_split, dim3(cnt), dim3(256), 0, c->stream, d, e, sc_stride, m, infos, ev, ev_stride);
-    } else {
-      HIPCHK(c, hipFuncSetAttribute((const void*)riptrm_eig::k_eig_lds<1024, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                    (int)shm));
-      hipLaunchKernelGGL((riptrm_eig::k_eig_lds<1024, 1>), dim3(cnt), dim3(1024), shm, c->stream, A, a_stride, lda, m, ev,
-                         ev_stride, d, e, sc_stride, R, r_stride, infos, vectors, nullptr);
-    }
+    HIPCHK(c, hipFuncSetAttribute((const void*)riptrm_eig::k_eig_lds<1024, 1>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)shm));
+    hipLaunchKernelGGL((riptrm_eig::k_eig_lds<1024, 1>), dim3(cnt), dim3(1024), shm, c->stream, A, a_stride, lda, m, ev,
+                       ev_stride, d, e, sc_stride, R, r_stride, infos, vectors, nullptr);
     HIPCHK(c, hipFuncSetAttribute((const void*)riptrm_eig::k_eig_lds<512, 2>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)shm));
     // the bisection over ~25 eigenvalues per workgroup up to order 128 (four waves of eight-lane
-    // groups instead of seven; kq stays 8 for any range <= 64, so the same arithmetic).
-    // RIPTRM_EIG_BIS=n (1..64): ~n per workgroup at every order (A/B)
-    const char* bs = getenv("RIPTRM_EIG_BIS");
-    const int bn = bs ? atoi(bs) : 0;
-    const int yb = (bn >= 1 && bn <= 64) ? (m + bn - 1) / bn : (m <= 128 ? (m + 24) / 25 : yv);
+    // groups instead of seven; kq stays 8 for any range <= 64, so the same arithmetic)
+    const int yb = m <= 128 ? (m + 24) / 25 : yv;
     hipLaunchKernelGGL((riptrm_eig::k_eig_lds<512, 2>), dim3(cnt, yb), dim3(512), shm,
                        c->stream, A, a_stride, lda, m, ev, ev_stride, d, e, sc_stride, R, r_stride, infos, vectors, nullptr);
     if (vectors) {
@@ -1485,23 +1443,20 @@ static int launch_eig(riptrm_ctx* c, int cnt, int m, double* A, int64_t a_stride
       hipLaunchKernelGGL((riptrm_eig::k_eig_lds<1024, 8>), dim3(cnt), dim3(1024), shm, c->stream, A, a_stride, lda, m, ev,
                          ev_stride, d, e, sc_stride, R, r_stride, infos, vectors, nullptr);
     }
-  } else if (!(t && atoi(t) == 512)) {
+  } else {
     HIPCHK(c, hipFuncSetAttribute((const void*)riptrm_eig::k_eig_lds<1024>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                   (int)shm));
     hipLaunchKernelGGL(riptrm_eig::k_eig_lds<1024>, dim3(cnt), dim3(1024), shm, c->stream, A, a_stride, lda, m, ev, ev_stride,
-                       d, e, sc_stride, R, r_stride, infos, vectors, stamps);
-  } else {
-    HIPCHK(c, hipFuncSetAttribute((const void*)riptrm_eig::k_eig_lds<512>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  (int)shm));
-    hipLaunchKernelGGL(riptrm_eig::k_eig_lds<512>, dim3(cnt), dim3(512), shm, c->stream, A, a_stride, lda, m, ev, ev_stride,
                        d, e, sc_stride, R, r_stride, infos, vectors, stamps);
   }
   HIPCHK(c, hipGetLastError());
   return RIPTRM_OK;
 }
 
+// A = Q diag(lam) Q^T for the pass's cnt slots (A at slot offset aoff, lda; eigenvalues ascending into
+// VS_EV, eigenvectors over A when vectors): the hand-written eigensolver where eig_compact(m) (compact
+// eigenvectors), rocSOLVER's batched dsyevd otherwise
 static int eig_batched(riptrm_ctx* c, const Bat& B, int cnt, bool vectors, int m, int64_t aoff, int lda) {
-  const char* e = getenv("RIPTRM_BIG_EIG");
   if (eig_compact(m)) {
     // hand-written: one workgroup per matrix, the matrix in LDS
     return launch_eig(c, cnt, m, B.base + aoff, B.sd, lda, B.base + off_vec(B.N, VS_EV), B.sd, B.base + off_vec(B.N, VS_R),
@@ -1512,23 +1467,8 @@ static int eig_batched(riptrm_ctx* c, const Bat& B, int cnt, bool vectors, int m
   const int ev = vectors ? EVECT_ORIGINAL : EVECT_NONE;
   double* A = B.base + aoff;
   double* W = B.base + off_vec(B.N, VS_EV);
-  int st;
-  if (e && e[0] == 'j' && s.syevj_sb) {
-    int32_t* sweeps = tail_of(c) + 2 * c->big_slots + 8;
-    double* resid = (double*)(tail_of(c) + tail_ints(c->big_slots));
-    st = s.syevj_sb(c->big_handle, ESORT_ASCENDING, ev, FILL_UPPER, m, A, lda, B.sd, 0.0, resid, 100, sweeps, W, B.sd,
-                    B.infos, cnt);
-  } else if (e && e[0] == 'd' && e[1] == 'j' && s.syevdj_sb) {
-    st = s.syevdj_sb(c->big_handle, ev, FILL_UPPER, m, A, lda, B.sd, W, B.sd, B.infos, cnt);
-  } else if (e && e[0] == 's' && s.syevd) {   // one rocsolver_dsyevd call per matrix
-    st = 0;
-    for (int k = 0; k < cnt && st == 0; ++k)
-      st = s.syevd(c->big_handle, ev, FILL_UPPER, m, A + k * B.sd, lda, W + k * B.sd, B.base + off_vec(B.N, VS_EW) + k * B.sd,
-                   B.infos + k);
-  } else {
-    st = s.syevd_sb(c->big_handle, ev, FILL_UPPER, m, A, lda, B.sd, W, B.sd, B.base + off_vec(B.N, VS_EW), B.sd, B.infos,
-                    cnt);
-  }
+  const int st = s.syevd_sb(c->big_handle, ev, FILL_UPPER, m, A, lda, B.sd, W, B.sd, B.base + off_vec(B.N, VS_EW), B.sd,
+                            B.infos, cnt);
   if (st != 0) return fail(c, RIPTRM_E_HIP, "rocsolver batched symmetric eigensolver failed (status " + std::to_string(st) + ")");
   return RIPTRM_OK;
 }
@@ -1545,9 +1485,8 @@ static int put_ids(riptrm_ctx* c, const Bat& B, const int32_t* ids, int cnt) {
 // latency floor) beats the grid-wide form's (3 launches ~12 us + the pass's matrices at ~5 TB/s)
 static bool cg_one_workgroup(int m, int cnt) {
   if (m > CG_WG_MAX) return false;
-  const char* e = getenv("RIPTRM_BIG_CG");   // "wg" / "grid": force one form (A/B measurements)
-  if (e && e[0] == 'w') return true;
-  if (e && e[0] == 'g') return false;
+  if (getenv_is("RIPTRM_BIG_CG", 'w')) return true;   // "wg" / "grid": force one form (A/B measurements)
+  if (getenv_is("RIPTRM_BIG_CG", 'g')) return false;
   const double bytes = (double)m * m * 8.0;
   const double t_wg = fmax(3e-6, bytes / 60e9);
   const double t_grid = 12e-6 + cnt * bytes / 5e12;
@@ -1562,7 +1501,7 @@ static int big_cg(riptrm_ctx* c, const Bat& B, int cnt, int64_t aoff, int lda, i
   hipStream_t st = c->stream;
   const int64_t N = B.N;
   const dim3 one(1, cnt), rows(blocks_of(m, GV / 64), cnt);
-  if (m <= CGW_MAX && cg_one_workgroup(m, cnt) && !getenv_is("RIPTRM_CG_WAVE", '0')) {
+  if (m <= CGW_MAX && cg_one_workgroup(m, cnt)) {
     const size_t shm = cg_wave_lds(m);
     HIPCHK(c, hipFuncSetAttribute((const void*)k_cg_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
     hipLaunchKernelGGL(k_cg_wave, one, dim3(64), shm, st, B, m, aoff, (int64_t)lda, D, dstride, nullptr, (int64_t)0, 0);
@@ -1645,33 +1584,42 @@ static int compact_trs(riptrm_ctx* c, const Bat& B, int cnt, int m, int64_t aoff
 }
 
 // ---- the tridiagonal path (riptrm_tri.h): orders above the one-workgroup eigensolver ------------------
-// RIPTRM_BIG_EIG unset (or 'h'): orders TRI_MIN .. TRI_MAX take it; otherwise rocSOLVER (A/B)
-// the tridiagonal path from order TRI_MIN = RIPTRM_TRS_TRI_MIN (RIPTRM_TRI_MIN=k: from k instead, 64 <= k
-// <= 200, A/B; 200 keeps the compact eigensolver at every order it serves)
-static bool tri_mode(int m) {
-  const char* e = getenv("RIPTRM_BIG_EIG");
-  const char* t = getenv("RIPTRM_TRI_MIN");
-  const int lo = t ? std::min(std::max(atoi(t), 64), riptrm_eig::EIG_LDS_MAX + 1) : riptrm_tri::TRI_MIN;
-  return m >= lo && m <= riptrm_tri::TRI_MAX && !(e && e[0] != 'h');
-}
+// orders TRI_MIN = RIPTRM_TRS_TRI_MIN .. TRI_MAX take it under the default routing
+static bool tri_mode(int m) { return m >= riptrm_tri::TRI_MIN && m <= riptrm_tri::TRI_MAX && eig_default_routing(); }
+
+// The clock stamps of one diagnostic launch (RIPTRM_TRI_STAMPS): a zeroed device buffer of n values that
+// the kernel fills through dev (null: off), fetched to the host after the launch and freed with the object.
+struct Stamps {
+  long long* dev = nullptr;
+  size_t n = 0;
+  Stamps() = default;
+  Stamps(const Stamps&) = delete;
+  Stamps& operator=(const Stamps&) = delete;
+  ~Stamps() {
+    if (dev) (void)hipFree(dev);
+  }
+  hipError_t alloc(size_t count, hipStream_t st) {
+    if (hipError_t e = hipMalloc(&dev, count * sizeof(long long))) return e;
+    n = count;
+    return hipMemsetAsync(dev, 0, n * sizeof(long long), st);
+  }
+  hipError_t fetch(std::vector<long long>& h, hipStream_t st) {   // synchronises
+    h.resize(n);
+    if (hipError_t e = hipMemcpyAsync(h.data(), dev, n * sizeof(long long), hipMemcpyDeviceToHost, st)) return e;
+    return hipStreamSynchronize(st);
+  }
+};
 
 template <int EL>
 static int tri_launch_el(riptrm_ctx* c, riptrm_tri::TriArgs a, int cnt, int m) {
-  constexpr int RW = 32 / EL;
-  int G = riptrm_tri::tri_groups(m);
-  auto kern = riptrm_tri::k_tridiag_dist<EL, RW>;
-  if (EL == 16 && getenv_is("RIPTRM_TRI_RW", '4')) {   // twice the rows per wave, half the workgroups (A/B;
-    kern = riptrm_tri::k_tridiag_dist<16, 4>;          // the granule layout's per-parity room covers it)
-    G = (m + 31) / 32;
-  }
+  const int G = riptrm_tri::tri_groups(m);
+  auto kern = riptrm_tri::k_tridiag_dist<EL>;
   int nb = 0;
   HIPCHK(c, hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, riptrm_tri::TT, 0));
   const int64_t cap = (int64_t)nb * c->ncu;
   if (nb < 1 || cap < G) return fail(c, RIPTRM_E_HIP, "tridiagonalisation: " + std::to_string(G) + " workgroups per matrix do not fit");
   const int per = (int)std::min<int64_t>(cnt, cap / G);   // matrices per cooperative launch
-  const char* spe = getenv("RIPTRM_TRI_SPREAD");   // granule lines every 128 << sp bytes (A/B)
-  a.spread = spe ? std::min(std::max(atoi(spe), 0), 8) : 0;
-  const size_t gbytes = (size_t)riptrm_tri::tri_grid_bytes(riptrm_tri::tri_granules(m) * per, a.spread);
+  const size_t gbytes = (size_t)riptrm_tri::tri_grid_bytes(riptrm_tri::tri_granules(m) * per);
   if (gbytes >= (size_t)INT32_MAX) return fail(c, RIPTRM_E_HIP, "tridiagonalisation: granule grid above 2 GiB");
   if (c->tri_grid_bytes < gbytes) {
     if (c->tri_grid) HIPCHK(c, hipFree(c->tri_grid));
@@ -1681,27 +1629,16 @@ static int tri_launch_el(riptrm_ctx* c, riptrm_tri::TriArgs a, int cnt, int m) {
     c->tri_grid_bytes = gbytes;
   }
   HIPCHK(c, hipMemsetAsync(a.infos, 0, (size_t)cnt * sizeof(int32_t), c->stream));
-  long long* stamps = nullptr;   // RIPTRM_TRI_STAMPS=1: phase cycles of matrix 0's workgroup 0 on stderr
-  if (getenv_is("RIPTRM_TRI_STAMPS", '1')) {
-    HIPCHK(c, hipMalloc(&stamps, 8 * sizeof(long long)));
-    HIPCHK(c, hipMemsetAsync(stamps, 0, 8 * sizeof(long long), c->stream));
-  }
-  a.stamps = stamps;
-  long long* hops = nullptr;   // RIPTRM_TRI_STAMPS=2: every workgroup's gather start / end every 16 steps
+  Stamps stamps;   // RIPTRM_TRI_STAMPS=1: phase cycles of matrix 0's workgroup 0 on stderr
+  if (getenv_is("RIPTRM_TRI_STAMPS", '1')) HIPCHK(c, stamps.alloc(8, c->stream));
+  a.stamps = stamps.dev;
+  Stamps hops;   // RIPTRM_TRI_STAMPS=2: every workgroup's gather start / end every 16 steps
   const int ns = (m + 15) / 16;
-  if (getenv_is("RIPTRM_TRI_STAMPS", '2')) {
-    HIPCHK(c, hipMalloc(&hops, (size_t)G * ns * 2 * sizeof(long long)));
-    HIPCHK(c, hipMemsetAsync(hops, 0, (size_t)G * ns * 2 * sizeof(long long), c->stream));
-  }
-  a.hops = hops;
-  {
-    const char* sl = getenv("RIPTRM_TRI_SLEEP");   // polling pace (A/B)
-    a.sleep = sl ? std::max(1, atoi(sl)) : 1;
-  }
+  if (getenv_is("RIPTRM_TRI_STAMPS", '2')) HIPCHK(c, hops.alloc((size_t)G * ns * 2, c->stream));
+  a.hops = hops.dev;
   for (int k0 = 0; k0 < cnt; k0 += per) {
     const int nk = std::min(per, cnt - k0);
-    HIPCHK(c, hipMemsetAsync(c->tri_grid, 0, (size_t)riptrm_tri::tri_grid_bytes(riptrm_tri::tri_granules(m) * nk, a.spread),
-                             c->stream));
+    HIPCHK(c, hipMemsetAsync(c->tri_grid, 0, (size_t)riptrm_tri::tri_grid_bytes(riptrm_tri::tri_granules(m) * nk), c->stream));
     a.k0 = k0;
     a.grid = c->tri_grid;
     a.grid_bytes = (int64_t)c->tri_grid_bytes;
@@ -1712,13 +1649,11 @@ static int tri_launch_el(riptrm_ctx* c, riptrm_tri::TriArgs a, int cnt, int m) {
     a.stamps = nullptr;
     a.hops = nullptr;
   }
-  if (hops) {
+  if (hops.dev) {
     // per sampled step: the publishers' skew (last - first gather start: a workgroup starts its
     // gather right after publishing) and each workgroup's wait past the last publisher
-    std::vector<long long> h((size_t)G * ns * 2);
-    HIPCHK(c, hipMemcpyAsync(h.data(), hops, h.size() * sizeof(long long), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(hops);
+    std::vector<long long> h;
+    HIPCHK(c, hops.fetch(h, c->stream));
     double skew = 0.0, lat = 0.0, own = 0.0, latmax = 0.0;
     int cntv = 0;
     for (int t = 1; t < ns - 1; ++t) {
@@ -1745,11 +1680,9 @@ static int tri_launch_el(riptrm_ctx* c, riptrm_tri::TriArgs a, int cnt, int m) {
               "mean %.2f max %.2f, gather (own start to end) %.2f\n", m, G, cntv, skew / cntv / 100.0, lat / cntv / 100.0,
               latmax / cntv / 100.0, own / cntv / 100.0);
   }
-  if (stamps) {
-    long long h[8];
-    HIPCHK(c, hipMemcpyAsync(h, stamps, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(stamps);
+  if (stamps.dev) {
+    std::vector<long long> h;
+    HIPCHK(c, stamps.fetch(h, c->stream));
     fprintf(stderr, "[tri stamps] m=%d G=%d cnt=%d gather %lld column %lld update %lld cycles (per step %.0f / %.0f / %.0f; "
             "column step: p.v %.0f, w and c %.0f, reflector %.0f)\n", m, G, cnt, h[0], h[1], h[2], h[0] / (double)(m - 1),
             h[1] / (double)(m - 1), h[2] / (double)(m - 1), h[4] / (double)(m - 2), h[5] / (double)(m - 2), h[6] / (double)(m - 2));
@@ -1785,46 +1718,20 @@ static int tri_tridiag(riptrm_ctx* c, const Bat& B, int cnt, int m, int64_t aoff
 
 // v <- H^T v / H v for the pass's slots (the tridiagonal path's reflectors): one 512-thread workgroup per
 // slot, 16 reflections per round (k_refl_blk; the rounds' compact-WY T blocks from k_refl_gram in the
-// slot's matrix area, dead once the tridiagonal T is formed: tri_finish makes them); RIPTRM_TRI_REFL=s one reflection per
-// round (k_refl_wg), =w one wave with the vector in registers (k_refl_big) (A/B)
+// slot's matrix area, dead once the tridiagonal T is formed: tri_finish makes them)
 static int tri_refl(riptrm_ctx* c, const Bat& B, int cnt, int m, int64_t voff, int64_t ooff, int backward) {
-  const dim3 grid(1, cnt);
-  if (!getenv_is("RIPTRM_TRI_REFL", 'w') && !getenv_is("RIPTRM_TRI_REFL", 's')) {
-    long long* stamps = nullptr;   // RIPTRM_TRI_STAMPS=3: slot 0's phase cycles on stderr
-    if (getenv_is("RIPTRM_TRI_STAMPS", '3')) {
-      HIPCHK(c, hipMalloc(&stamps, 4 * sizeof(long long)));
-      HIPCHK(c, hipMemsetAsync(stamps, 0, 4 * sizeof(long long), c->stream));
-    }
-    if (getenv_is("RIPTRM_TRI_REFL_E", '1'))
-      hipLaunchKernelGGL(riptrm_tri::k_refl_blk<1>, grid, dim3(1024), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N),
-                         (int64_t)0, voff, ooff, backward, stamps);
-    else
-      hipLaunchKernelGGL(riptrm_tri::k_refl_blk<2>, grid, dim3(512), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N),
-                         (int64_t)0, voff, ooff, backward, stamps);
-    HIPCHK(c, hipGetLastError());
-    if (stamps) {
-      long long h[4];
-      HIPCHK(c, hipMemcpyAsync(h, stamps, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      (void)hipFree(stamps);
-      const int nb = riptrm_tri::refl_blocks(m);
-      fprintf(stderr, "[refl stamps] m=%d rounds=%d per round: operands + dots %.0f, solve %.0f, update %.0f cycles\n", m, nb,
-              h[0] / (double)nb, h[1] / (double)nb, h[2] / (double)nb);
-    }
-    return RIPTRM_OK;
-  }
-  if (getenv_is("RIPTRM_TRI_REFL", 's')) {
-    hipLaunchKernelGGL(riptrm_tri::k_refl_wg, grid, dim3(1024), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N), voff, ooff,
-                       backward);
-    HIPCHK(c, hipGetLastError());
-    return RIPTRM_OK;
-  }
-  switch (riptrm_tri::tri_el(m)) {
-    case 4: hipLaunchKernelGGL(riptrm_tri::k_refl_big<4>, grid, dim3(64), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N), voff, ooff, backward); break;
-    case 8: hipLaunchKernelGGL(riptrm_tri::k_refl_big<8>, grid, dim3(64), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N), voff, ooff, backward); break;
-    default: hipLaunchKernelGGL(riptrm_tri::k_refl_big<16>, grid, dim3(64), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N), voff, ooff, backward); break;
-  }
+  Stamps stamps;   // RIPTRM_TRI_STAMPS=3: slot 0's phase cycles on stderr
+  if (getenv_is("RIPTRM_TRI_STAMPS", '3')) HIPCHK(c, stamps.alloc(4, c->stream));
+  hipLaunchKernelGGL(riptrm_tri::k_refl_blk<2>, dim3(1, cnt), dim3(512), 0, c->stream, B.base, B.sd, 0, m, off_refl(B.N),
+                     (int64_t)0, voff, ooff, backward, stamps.dev);
   HIPCHK(c, hipGetLastError());
+  if (stamps.dev) {
+    std::vector<long long> h;
+    HIPCHK(c, stamps.fetch(h, c->stream));
+    const int nb = riptrm_tri::refl_blocks(m);
+    fprintf(stderr, "[refl stamps] m=%d rounds=%d per round: operands + dots %.0f, solve %.0f, update %.0f cycles\n", m, nb,
+            h[0] / (double)nb, h[1] / (double)nb, h[2] / (double)nb);
+  }
   return RIPTRM_OK;
 }
 
@@ -1837,21 +1744,16 @@ static int tri_solve_el(riptrm_ctx* c, const Bat& B, int cnt, int m, const doubl
   HIPCHK(c, hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
   const riptrm_tri::TriSc S{SC_CG_OK, SC_P1OBJ, SC_KIND, SC_LAM1, SC_MINEIG, SC_INTERIOR, SC_DELTA, SC_AN, SC_ATOL, SC_IT,
                             SC_DONE, SC_TRI_FB, SC_RHO_PREV};   // (SC_RHO_PREV: the Newton steps, diagnostics)
-  long long* stamps = nullptr;   // RIPTRM_TRI_STAMPS=1: slot 0's phase clocks on stderr
-  if (getenv_is("RIPTRM_TRI_STAMPS", '1')) {
-    HIPCHK(c, hipMalloc(&stamps, 10 * sizeof(long long)));
-    HIPCHK(c, hipMemsetAsync(stamps, 0, 10 * sizeof(long long), c->stream));
-  }
+  Stamps stamps;   // RIPTRM_TRI_STAMPS=1: slot 0's phase clocks on stderr
+  if (getenv_is("RIPTRM_TRI_STAMPS", '1')) HIPCHK(c, stamps.alloc(10, c->stream));
   hipLaunchKernelGGL(kern, dim3(1, cnt), dim3(256), shm, c->stream, B.base, B.sd, B.infos, m, off_vec(N, VS_R),
                      off_vec(N, VS_P), off_vec(N, VS_G), off_vec(N, VS_A), off_vec(N, VS_PE), off_vec(N, VS_CGX),
                      off_vec(N, VS_EV), off_sc(N), S, D, dstride, B.ids, tolhc, mode, cg_skip ? 1 : 0, eig_known ? 1 : 0,
-                     getenv_is("RIPTRM_TRI_SERIAL", '1') ? 1 : 0, stamps);
+                     getenv_is("RIPTRM_TRI_SERIAL", '1') ? 1 : 0, stamps.dev);
   HIPCHK(c, hipGetLastError());
-  if (stamps) {
-    long long h[10];
-    HIPCHK(c, hipMemcpyAsync(h, stamps, sizeof(h), hipMemcpyDeviceToHost, c->stream));
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    (void)hipFree(stamps);
+  if (stamps.dev) {
+    std::vector<long long> h;
+    HIPCHK(c, stamps.fetch(h, c->stream));
     if (h[0] && mode == 0) {
       const long long par = std::max(std::max(h[2], h[3]), h[8]);   // the concurrent phases' end
       fprintf(stderr, "[tri_solve stamps] m=%d mode=0 eig %lld hard %lld newton %lld (%lld steps) skip-test %lld cg %lld "
@@ -2169,7 +2071,7 @@ int riptrm_big_gep_ids(riptrm_ctx* c, int dim, const int32_t* sel, int count, co
                          dim, off_vec(N, cpt ? VS_PE : VS_A), off_vec(N, VS_G), (int64_t)-1);
       hipLaunchKernelGGL(k_set_delta, dim3(blocks_of(cnt, 64)), dim3(64), 0, st, Bt, cnt, Delta, (int64_t)1);
       hipLaunchKernelGGL(k_secular, dim3(1, cnt), dim3(WG), 0, st, Bt, dim, tolhc, 0);
-      if (dim <= CGW_MAX && !getenv_is("RIPTRM_CG_WAVE", '0')) {
+      if (dim <= CGW_MAX) {
         const size_t shm = cg_wave_lds(dim);
         HIPCHK(c, hipFuncSetAttribute((const void*)k_cg_wave, hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
         hipLaunchKernelGGL(k_cg_wave, dim3(1, cnt), dim3(64), shm, st, Bt, dim, (int64_t)0, lda, Delta, (int64_t)1, A,
@@ -2316,17 +2218,14 @@ int riptrm_sym_eig(riptrm_ctx* ctx, int32_t dim, int32_t batch, double* A, int64
     ctx->eig_scratch_bytes = need;
   }
   double* s = (double*)ctx->eig_scratch;
-  long long* stamps = nullptr;   // RIPTRM_EIG_STAMPS=1: per-phase clocks of matrix 0 on stderr (diagnostics)
-  const bool want_stamps = getenv_is("RIPTRM_EIG_STAMPS", '1');
-  if (want_stamps) HIPCHK(ctx, hipMalloc(&stamps, (size_t)batch * 8 * sizeof(long long)));
+  Stamps stamps;   // RIPTRM_EIG_STAMPS=1: per-phase clocks of matrix 0 on stderr (diagnostics)
+  if (getenv_is("RIPTRM_EIG_STAMPS", '1')) HIPCHK(ctx, stamps.alloc((size_t)batch * 8, ctx->stream));
   if (int rc = launch_eig(ctx, batch, dim, A, a_stride, (int)lda, w, w_stride, s, s + sc, per, s + 2 * sc, per, info,
-                          vectors == 2 ? 2 : (vectors ? 1 : 0), stamps))
+                          vectors == 2 ? 2 : (vectors ? 1 : 0), stamps.dev))
     return rc;
-  if (want_stamps) {
-    std::vector<long long> h((size_t)batch * 8);
-    HIPCHK(ctx, hipMemcpyAsync(h.data(), stamps, h.size() * sizeof(long long), hipMemcpyDeviceToHost, ctx->stream));
-    HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
-    (void)hipFree(stamps);
+  if (stamps.dev) {
+    std::vector<long long> h;
+    HIPCHK(ctx, stamps.fetch(h, ctx->stream));
     const long long* t = h.data();
     fprintf(stderr, "[eig stamps] m=%d load+tridiag %lld (reflector %lld symv %lld) bisect %lld vectors(twisted+backtransform) %lld "
             "orthog %lld total %lld\n",

@@ -5,7 +5,8 @@
 subproblems held as torch tensors on the GPU (dim <= RIPTRM_TRS_DIM_MAX: one launch, the matrix in
 LDS; larger: the HBM path — up to dim 149 the hand-written eigensolver and SciPy's CG restated in its
 eigen-coordinates, 150..1024 the cooperative tridiagonalisation and the subproblem in T's coordinates,
-rocSOLVER dsyevd above and for hard cases; the secular Newton — every subproblem of the batch in one
+whose hard cases go back to an eigendecomposition (the hand-written eigensolver at 150..199, rocSOLVER
+dsyevd at 200..1024), rocSOLVER dsyevd above 1024; the secular Newton — every subproblem of the batch in one
 pass when the scratch budget allows).  Only B = I is supported — the one call site passes ``np.eye(xdim)``
 (RIPTRM.py:441).  No CPU fallback.
 """
