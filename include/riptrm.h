@@ -229,6 +229,26 @@ int64_t riptrm_sup_unit_bytes(int32_t n, int32_t unit);
 int64_t riptrm_sup_deal(int32_t n, int32_t balanced, int32_t nact, int32_t grid, int32_t* wg, int32_t* slot,
                         int32_t* unit, int64_t cap);
 
+/* ---- the packed copy of S streamed by the super-tile S-pass (csrc/riptrm_spack.h) ----
+ * Host mirrors of the format, the same functions the kernels call.  A block is one wave's 16 rows x
+ * 128 columns of a full tile (`rows`: 16 x 128 doubles, row stride 128) in 14,848 bytes.
+ * Bytes one S-pass reads per instance with every full tile packed; -1 for a bad argument. */
+int64_t riptrm_spack_pass_bytes(int32_t n);
+/* Bytes of one packed 128 x 128 tile (8 blocks). */
+int32_t riptrm_spack_tile_bytes(void);
+/* Tile classifier over `count` doubles: returns the tile word (0 = stays plain, else the exponent
+ * base) and, if `range` is given, {smallest, largest biased exponent field among the normal
+ * numbers, 1 if an Inf or NaN was seen}. */
+int32_t riptrm_spack_classify(const double* v, int64_t count, int32_t range[3]);
+/* Encode / decode one block with exponent base `ebase`.  encode returns -1 if an element cannot be
+ * encoded with that base (the output is then unspecified). */
+int riptrm_spack_encode_block(const double* rows, int32_t ebase, void* out);
+int riptrm_spack_decode_block(const void* in, int32_t ebase, double* rows);
+/* After bind: {packed copy in use (0 | 1), stored tiles streamed packed, stored tiles streamed
+ * plain, device bytes the library holds for the copy, elements that failed the bind-time check
+ * (RIPTRM_SPACK_VERIFY=1; -1 if it did not run)}.  Waits for the context's stream. */
+int riptrm_spass_packed_info(riptrm_ctx* ctx, int64_t out[5]);
+
 /* ---- data preparation ---- */
 /* S_b <- pack(Z_b + Z_b^T) for b < count: Z_b is n x n row-major with leading dimension ldz at
  * Z + b*z_stride, S_b is written at S + b*s_stride in `layout` with zero padding.  Each

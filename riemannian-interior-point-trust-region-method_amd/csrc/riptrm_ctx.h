@@ -43,6 +43,12 @@ struct riptrm_ctx {
                               // 2 = super-tile always, 3 = automatic with bind-time timing
   int sup_auto = 1;           // kind 3: the super-tile kernel won the bind-time calibration
   float spass_cal_ms[2] = {0.0f, 0.0f};   // calibration: ms per launch of the per-tile / super-tile kernel
+  // the packed copy of S's full tiles streamed by k_spass_sup (riptrm_spack.h): library-owned, built at
+  // bind, freed on rebind and destroy; P.spk / P.spk_word point into it while it is in use
+  char* spk = nullptr;
+  int32_t* spk_word = nullptr;   // tile words, then the verify kernel's mismatch counter
+  size_t spk_bytes = 0;
+  bool spk_verified = false;     // RIPTRM_SPACK_VERIFY=1 ran since bind
   std::vector<int32_t> sup_perm;   // host copy of the workspace's [perm] region (the upload's source)
   // optional HIP-event timing of every k_gemv / k_state launch (riptrm_profile_*)
   // Two event pools: a chunk of lock-step iterations records into pool ev_cur; its pairs are folded

@@ -255,6 +255,11 @@ struct DevParams {
   int32_t smode;        // per launch: 0 = tile S-pass (grid [nt][nt][TS]), 1 = super-tile ([nst][nst][SW])
   const int32_t* sup_perm;   // static deal: nullptr = the units in index order, u = g, g + G, ... (default);
                         // else the units largest first, dealt back and forth (RIPTRM_SUP_BALANCED=1)
+  // the packed copy of S's full tiles that k_spass_sup streams (riptrm_spack.h); all zero without one
+  const char* spk;           // instance b's tile t at spk + b spk_stride + t SPK_TILE_BYTES
+  int64_t spk_stride;        // bytes between instances
+  const int32_t* spk_word;   // [batch][spk_nfull] tile words: 0 = read the tile from plain S, else its ebase
+  int32_t spk_ntf, spk_nfull;   // full tiles per dimension / per instance
   double* pbuf;         // S-pass partial sums: 2 x pbatch x pgrid_of(n) (symmetric-tile layout),
                         // MM_KZ x 2 x batch x ld (shared layout)
   int32_t pbatch;       // instances of the partial grid (= batch; the persistent replicas' parameter

@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <type_traits>
 #include "riptrm_device.h"
+#include "riptrm_spack.h"
 #include "riptrm_ctx.h"
 #include "riptrm_wave.h"
 #include "riptrm_trs.h"
@@ -354,11 +355,45 @@ __global__ void __launch_bounds__(SP_THREADS, 4) k_spass_sym(DevParams P, int li
 // 7.15 without, 6.79-6.82 for this kernel on the same box).  Partial grid [b][P][Q][SW]: slot
 // (P, Q) holds unit (P, Q)'s row part (P <= Q; the whole symmetric block on the diagonal) and
 // slot (Q, P) its column part; every slot is written by exactly one unit: deterministic.
+// Tile source: with a packed copy bound (P.spk, riptrm_spack.h) a full tile whose tile word is not 0
+// streams as the wave's 14,848-byte block (15 loads instead of 16, 9.4% fewer bytes) and is decoded,
+// bit for bit, 8 rows at a time just ahead of their FMAs; edge tiles and tiles that do not pack take
+// the plain loads.  Both sources feed sup_rows, so the sums are the same bits either way.
 // ------------------------------------------------------------------------------------------
 constexpr int SUP_OCAP = 15360;                 // doubles of buffered unit results (120 KiB)
 constexpr int SUP_MAXU = SUP_OCAP / (2 * SW);   // units per burst at one right-hand side
 
 typedef double (*sup_red_t)[SP_WAVES][SW];
+typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+typedef uint32_t u32x2 __attribute__((ext_vector_type(2)));
+
+// One 8-row batch of a tile against the unit's right-hand sides: the row part goes to r0 / r1 (8-lane
+// reduce-scatter), the column part accumulates in c0 / c1.  Shared by the plain and the packed tile
+// source, so both add the same products in the same order.
+template <int NR>
+__device__ __forceinline__ void sup_rows(const dbl2 (&sv)[8], const double* vi0, const double* vi1, dbl2 vj0, dbl2 vj1,
+                                         double& c0x, double& c0y, double& c1x, double& c1y, double& r0, double& r1) {
+  double a[8];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const double vi = vi0[k];
+    a[k] = __builtin_fma(sv[k].y, vj0.y, sv[k].x * vj0.x);
+    c0x = __builtin_fma(sv[k].x, vi, c0x);
+    c0y = __builtin_fma(sv[k].y, vi, c0y);
+  }
+  r0 += reduce_scatter8(a);
+  if (NR == 2) {
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+      const double vi = vi1[k];
+      a[k] = __builtin_fma(sv[k].y, vj1.y, sv[k].x * vj1.x);
+      c1x = __builtin_fma(sv[k].x, vi, c1x);
+      c1y = __builtin_fma(sv[k].y, vi, c1y);
+    }
+    r1 += reduce_scatter8(a);
+  }
+}
+
 
 template <int NR>
 // One right-hand side: the wave's 16 row entries of v for tile row I are loaded once per tile row
@@ -381,6 +416,17 @@ __device__ __forceinline__ void sup_unit(const DevParams& P, int b, int Pq, int 
   for (int k = 0; k < NR; ++k)
 #pragma unroll
     for (int i = 0; i < SB; ++i) racc[k][i][0] = racc[k][i][1] = 0.0;
+  // tile words of the unit's (up to) SB x SB tiles, loaded together ahead of everything else: 0 = plain
+  // S (always, without a packed copy: ntf = 0), else the tile's exponent base
+  const int ntf = P.spk_ntf;
+  int32_t tw[SB][SB];
+#pragma unroll
+  for (int il = 0; il < SB; ++il)
+#pragma unroll
+    for (int jl = 0; jl < SB; ++jl) {
+      const int I = SB * Pq + il, J = SB * Qq + jl;
+      tw[il][jl] = (J >= I && J < ntf) ? P.spk_word[(int64_t)b * P.spk_nfull + spk_tile_index(I, J, ntf)] : 0;
+    }
   if (NR == 2) __syncthreads();   // the previous unit's reduction may still read either buffer
   const int r0sel = NR == 2 ? 0 : rsel;
 #pragma unroll
@@ -421,39 +467,57 @@ __device__ __forceinline__ void sup_unit(const DevParams& P, int b, int Pq, int 
       }
       __builtin_amdgcn_sched_barrier(0);   // keep the vector loads ahead of the S rows
       double c0x = 0.0, c0y = 0.0, c1x = 0.0, c1y = 0.0;
-      dbl2 sv2[ROWS / 8][8];
+      const int32_t ebase = jl ? tw[il][SB - 1] : tw[il][0];
+      if (ebase != 0) {   // wave-uniform: this tile streams from the packed copy (riptrm_spack.h), a full tile
+        const char* __restrict__ blk = P.spk + (int64_t)b * P.spk_stride +
+                                       (int64_t)spk_tile_index(I, J, ntf) * SPK_TILE_BYTES + w * SPK_BLOCK_BYTES;
+        // the block's 15 loads, batch 0's slabs first; decoded batch by batch just before the FMAs
+        uint32_t lo[SPK_ELEMS], hs[SPK_HI_DWORDS];
 #pragma unroll
-      for (int rb = 0; rb < ROWS / 8; ++rb)
+        for (int h = 0; h < 2; ++h) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const int row = w * ROWS + rb * 8 + k;
-          const bool ok = cl && row < rowsT;   // corner / narrow tiles: not stored
-          const dbl2 x = __builtin_nontemporal_load((const dbl2*)(T + (row < rowsT ? row : 0) * colsT + (cl ? 2 * lane : 0)));
-          sv2[rb][k] = ok ? x : dbl2{0.0, 0.0};
+          for (int s = 4 * h; s < 4 * h + 4; ++s) {
+            const u32x4 x = __builtin_nontemporal_load((const u32x4*)(blk + s * 1024) + lane);
+            lo[4 * s] = x.x; lo[4 * s + 1] = x.y; lo[4 * s + 2] = x.z; lo[4 * s + 3] = x.w;
+          }
+#pragma unroll
+          for (int s = 4 * h; s < (h ? 7 : 4); ++s) {
+            if (s < 6) {
+              const u32x4 x = __builtin_nontemporal_load((const u32x4*)(blk + SPK_LO_BYTES + s * 1024) + lane);
+              hs[4 * s] = x.x; hs[4 * s + 1] = x.y; hs[4 * s + 2] = x.z; hs[4 * s + 3] = x.w;
+            } else {
+              const u32x2 x = __builtin_nontemporal_load((const u32x2*)(blk + SPK_LO_BYTES + SPK_HI4_BYTES) + lane);
+              hs[24] = x.x; hs[25] = x.y;
+            }
+          }
         }
 #pragma unroll
-      for (int rb = 0; rb < ROWS / 8; ++rb) {
-        const int r0 = w * ROWS + rb * 8;
-        if (r0 >= rowsT) break;   // wave-uniform
-        const dbl2 (&sv)[8] = sv2[rb];
-        double a[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) {
-          const double vi = vi0[rb * 8 + k];
-          a[k] = __builtin_fma(sv[k].y, vj0.y, sv[k].x * vj0.x);
-          c0x = __builtin_fma(sv[k].x, vi, c0x);
-          c0y = __builtin_fma(sv[k].y, vi, c0y);
-        }
-        racc[0][il][rb] += reduce_scatter8(a);
-        if (NR == 2) {
+        for (int rb = 0; rb < ROWS / 8; ++rb) {
+          dbl2 sv[8];
 #pragma unroll
           for (int k = 0; k < 8; ++k) {
-            const double vi = vi1[rb * 8 + k];
-            a[k] = __builtin_fma(sv[k].y, vj1.y, sv[k].x * vj1.x);
-            c1x = __builtin_fma(sv[k].x, vi, c1x);
-            c1y = __builtin_fma(sv[k].y, vi, c1y);
+            const int e = 16 * rb + 2 * k;
+            sv[k].x = __hiloint2double((int)spk_dec_hi(spk_get(hs, e), ebase), (int)lo[e]);
+            sv[k].y = __hiloint2double((int)spk_dec_hi(spk_get(hs, e + 1), ebase), (int)lo[e + 1]);
           }
-          racc[NR - 1][il][rb] += reduce_scatter8(a);
+          sup_rows<NR>(sv, vi0 + rb * 8, vi1 + rb * 8, vj0, vj1, c0x, c0y, c1x, c1y, racc[0][il][rb], racc[NR - 1][il][rb]);
+        }
+      } else {
+        dbl2 sv2[ROWS / 8][8];
+#pragma unroll
+        for (int rb = 0; rb < ROWS / 8; ++rb)
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const int row = w * ROWS + rb * 8 + k;
+            const bool ok = cl && row < rowsT;   // corner / narrow tiles: not stored
+            const dbl2 x = __builtin_nontemporal_load((const dbl2*)(T + (row < rowsT ? row : 0) * colsT + (cl ? 2 * lane : 0)));
+            sv2[rb][k] = ok ? x : dbl2{0.0, 0.0};
+          }
+#pragma unroll
+        for (int rb = 0; rb < ROWS / 8; ++rb) {
+          const int r0 = w * ROWS + rb * 8;
+          if (r0 >= rowsT) break;   // wave-uniform
+          sup_rows<NR>(sv2[rb], vi0 + rb * 8, vi1 + rb * 8, vj0, vj1, c0x, c0y, c1x, c1y, racc[0][il][rb], racc[NR - 1][il][rb]);
         }
       }
       if (I != J) {   // column part (the diagonal tile is stored whole: row part only)
@@ -553,6 +617,70 @@ __global__ void __launch_bounds__(SP_THREADS, 1) k_spass_sup(DevParams P, int li
     q = sup_deal_item(++round, (int)blockIdx.x, (int)gridDim.x, perm != nullptr);
   }
   if (nslot > 0) sup_flush(P, outb, meta, nslot, list_in);
+}
+
+// Build the packed copy at bind (riptrm_spack.h): one workgroup per (full tile, instance), every lane
+// on the 32 elements the S-pass gives it.  Pass 1 folds the tile's exponent range through LDS, pass 2
+// writes the tile word and, for a tile that packs, the wave's block.  VERIFY: decode the stored block
+// as the S-pass does and count the elements whose 64 bits differ from plain S.
+template <bool VERIFY>
+__global__ void __launch_bounds__(SP_THREADS) k_spack(DevParams P, char* spk, int32_t* word, unsigned long long* mism) {
+  __shared__ int sh[3];   // emin, emax, bad
+  const int lane = (int)__lane_id();
+  const int w = threadIdx.x >> 6;
+  const int b = blockIdx.y, ntf = P.spk_ntf;
+  int I, J;
+  tile_ij((int)blockIdx.x, ntf, I, J);
+  const double* __restrict__ T = P.S + (int64_t)b * P.inst_stride + sym_off(I, J, P.nt, P.wl);
+  char* blk = spk + (int64_t)b * P.spk_stride + (int64_t)blockIdx.x * SPK_TILE_BYTES + w * SPK_BLOCK_BYTES;
+  int32_t* tword = word + (int64_t)b * P.spk_nfull + blockIdx.x;
+  uint32_t lo[SPK_ELEMS], hi[SPK_ELEMS];
+#pragma unroll
+  for (int e = 0; e < SPK_ELEMS; e += 2) {
+    const dbl2 x = *(const dbl2*)(T + spk_row(w, e) * TS + 2 * lane);
+    lo[e] = (uint32_t)__double2loint(x.x); hi[e] = (uint32_t)__double2hiint(x.x);
+    lo[e + 1] = (uint32_t)__double2loint(x.y); hi[e + 1] = (uint32_t)__double2hiint(x.y);
+  }
+  if (VERIFY) {
+    const int32_t ebase = *tword;
+    if (ebase == 0) return;   // workgroup-uniform
+    uint32_t hs[SPK_HI_DWORDS];
+#pragma unroll
+    for (int j = 0; j < SPK_HI_DWORDS; ++j) hs[j] = *(const uint32_t*)(blk + spk_hi_off(j, lane));
+    int bad = 0;
+#pragma unroll
+    for (int e = 0; e < SPK_ELEMS; ++e)
+      bad += (*(const uint32_t*)(blk + spk_lo_off(e, lane)) != lo[e]) || (spk_dec_hi(spk_get(hs, e), ebase) != hi[e]);
+    if (bad) atomicAdd(mism, (unsigned long long)bad);
+    return;
+  }
+  if (threadIdx.x == 0) { sh[0] = 0x7FF; sh[1] = 0; sh[2] = 0; }
+  __syncthreads();
+  int emin = 0x7FF, emax = 0, bad = 0;
+#pragma unroll
+  for (int e = 0; e < SPK_ELEMS; ++e) spk_range_add(hi[e], emin, emax, bad);
+  atomicMin(&sh[0], emin);
+  atomicMax(&sh[1], emax);
+  if (bad) atomicOr(&sh[2], 1);
+  __syncthreads();
+  const int32_t ebase = spk_tile_word(sh[0], sh[1], sh[2]);
+  if (threadIdx.x == 0) *tword = ebase;
+  if (ebase == 0) return;
+  uint32_t hs[SPK_HI_DWORDS];
+#pragma unroll
+  for (int j = 0; j < SPK_HI_DWORDS; ++j) hs[j] = 0u;
+#pragma unroll
+  for (int e = 0; e < SPK_ELEMS; ++e) {
+    uint32_t f;
+    (void)spk_enc_hi(hi[e], ebase, f);
+    spk_put(hs, e, f);
+  }
+#pragma unroll
+  for (int s = 0; s < 8; ++s) *((u32x4*)(blk + s * 1024) + lane) = u32x4{lo[4 * s], lo[4 * s + 1], lo[4 * s + 2], lo[4 * s + 3]};
+#pragma unroll
+  for (int s = 0; s < 6; ++s)
+    *((u32x4*)(blk + SPK_LO_BYTES + s * 1024) + lane) = u32x4{hs[4 * s], hs[4 * s + 1], hs[4 * s + 2], hs[4 * s + 3]};
+  *((u32x2*)(blk + SPK_LO_BYTES + SPK_HI4_BYTES) + lane) = u32x2{hs[24], hs[25]};
 }
 
 // ------------------------------------------------------------------------------------------
@@ -3025,6 +3153,69 @@ static void sup_perm_of(int32_t n, std::vector<int32_t>& perm) {
   std::stable_sort(perm.begin(), perm.end(), [&](int32_t a, int32_t b) { return bytes[a] > bytes[b]; });
 }
 
+// ---- the packed copy of S (riptrm_spack.h): library-owned device memory, built at bind ----
+static void spack_release(riptrm_ctx* c) {
+  if (c->spk) (void)hipFree(c->spk);
+  if (c->spk_word) (void)hipFree(c->spk_word);
+  c->spk = nullptr;
+  c->spk_word = nullptr;
+  c->spk_bytes = 0;
+  c->spk_verified = false;
+  c->P.spk = nullptr;
+  c->P.spk_word = nullptr;
+  c->P.spk_stride = 0;
+  c->P.spk_ntf = c->P.spk_nfull = 0;
+}
+
+// the mismatch counter sits behind the tile words
+static unsigned long long* spack_mism(const riptrm_ctx* c) {
+  return (unsigned long long*)(c->spk_word + round_up((int64_t)c->P.batch * c->P.spk_nfull, 4));
+}
+
+// (re)pack instances [b0, b0 + count) from plain S on the context's stream
+static int spack_pack(riptrm_ctx* c, int b0, int count) {
+  DevParams Q = c->P;
+  Q.S = c->P.S + (int64_t)b0 * c->P.inst_stride;
+  char* spk = c->spk + (int64_t)b0 * c->P.spk_stride;
+  int32_t* word = c->spk_word + (int64_t)b0 * c->P.spk_nfull;
+  const dim3 grid((unsigned)c->P.spk_nfull, (unsigned)count);
+  hipLaunchKernelGGL(k_spack<false>, grid, dim3(SP_THREADS), 0, c->stream, Q, spk, word, (unsigned long long*)nullptr);
+  HIPCHK(c, hipGetLastError());
+  if (getenv_is("RIPTRM_SPACK_VERIFY", '1')) {
+    hipLaunchKernelGGL(k_spack<true>, grid, dim3(SP_THREADS), 0, c->stream, Q, spk, word, spack_mism(c));
+    HIPCHK(c, hipGetLastError());
+    c->spk_verified = true;
+  }
+  return RIPTRM_OK;
+}
+
+// bind: RIPTRM_SPASS_PACKED unset = where the automatic rule streams with k_spass_sup (sup_min_units
+// units per instance), 0 = never, 1 = every symmetric-tile bind.  No memory for it: no packed copy.
+static int spack_build(riptrm_ctx* c, int sup_min_units) {
+  DevParams& P = c->P;
+  if (P.layout != RIPTRM_LAYOUT_SYMTILE) return RIPTRM_OK;
+  const char* ev = getenv("RIPTRM_SPASS_PACKED");
+  const bool want = ev && ev[0] ? ev[0] == '1' : P.nsup >= sup_min_units;
+  const int64_t nfull = spk_nfull_of(P.n);
+  if (!want || nfull == 0 || P.batch > 65535) return RIPTRM_OK;
+  const size_t bytes = (size_t)P.batch * nfull * SPK_TILE_BYTES;
+  const size_t wbytes = (size_t)round_up((int64_t)P.batch * nfull, 4) * 4 + 16;
+  if (hipMalloc((void**)&c->spk, bytes) != hipSuccess || hipMalloc((void**)&c->spk_word, wbytes) != hipSuccess) {
+    (void)hipGetLastError();
+    spack_release(c);
+    return RIPTRM_OK;
+  }
+  c->spk_bytes = bytes + wbytes;
+  P.spk_ntf = spk_ntf_of(P.n);
+  P.spk_nfull = (int32_t)nfull;
+  P.spk_stride = nfull * SPK_TILE_BYTES;
+  HIPCHK(c, hipMemsetAsync(c->spk_word, 0, wbytes, c->stream));
+  if (int rc = spack_pack(c, 0, P.batch)) return rc;
+  P.spk = c->spk;
+  P.spk_word = c->spk_word;
+  return RIPTRM_OK;
+}
+
 extern "C" {
 
 int riptrm_abi_version(void) { return RIPTRM_ABI_VERSION; }
@@ -3054,6 +3245,78 @@ int64_t riptrm_sup_deal(int32_t n, int32_t balanced, int32_t nact, int32_t grid,
       ++cnt;
     }
   return cnt;
+}
+
+// ---- host mirrors of the packed format (riptrm_spack.h: the functions the kernels call) ----
+int64_t riptrm_spack_pass_bytes(int32_t n) { return n < 2 ? -1 : spk_pass_bytes(n); }
+int32_t riptrm_spack_tile_bytes(void) { return SPK_TILE_BYTES; }
+
+int32_t riptrm_spack_classify(const double* v, int64_t count, int32_t range[3]) {
+  if (!v || count < 0) return 0;
+  int emin = 0x7FF, emax = 0, bad = 0;
+  for (int64_t i = 0; i < count; ++i) {
+    uint64_t u;
+    std::memcpy(&u, v + i, 8);
+    spk_range_add((uint32_t)(u >> 32), emin, emax, bad);
+  }
+  if (range) { range[0] = emin; range[1] = emax; range[2] = bad; }
+  return spk_tile_word(emin, emax, bad);
+}
+
+int riptrm_spack_encode_block(const double* rows, int32_t ebase, void* out) {
+  if (!rows || !out) return -1;
+  int rc = 0;
+  for (int lane = 0; lane < 64; ++lane) {
+    uint32_t hs[SPK_HI_DWORDS] = {0};
+    for (int e = 0; e < SPK_ELEMS; ++e) {
+      uint64_t u;
+      std::memcpy(&u, rows + spk_row(0, e) * TS + spk_col(lane, e), 8);
+      uint32_t f, lo = (uint32_t)u;
+      if (!spk_enc_hi((uint32_t)(u >> 32), ebase, f)) rc = -1;
+      spk_put(hs, e, f & 0x3FFFFFFu);
+      std::memcpy((char*)out + spk_lo_off(e, lane), &lo, 4);
+    }
+    for (int j = 0; j < SPK_HI_DWORDS; ++j) std::memcpy((char*)out + spk_hi_off(j, lane), &hs[j], 4);
+  }
+  return rc;
+}
+
+int riptrm_spack_decode_block(const void* in, int32_t ebase, double* rows) {
+  if (!rows || !in) return -1;
+  for (int lane = 0; lane < 64; ++lane) {
+    uint32_t hs[SPK_HI_DWORDS];
+    for (int j = 0; j < SPK_HI_DWORDS; ++j) std::memcpy(&hs[j], (const char*)in + spk_hi_off(j, lane), 4);
+    for (int e = 0; e < SPK_ELEMS; ++e) {
+      uint32_t lo;
+      std::memcpy(&lo, (const char*)in + spk_lo_off(e, lane), 4);
+      const uint64_t u = ((uint64_t)spk_dec_hi(spk_get(hs, e), ebase) << 32) | lo;
+      std::memcpy(rows + spk_row(0, e) * TS + spk_col(lane, e), &u, 8);
+    }
+  }
+  return 0;
+}
+
+int riptrm_spass_packed_info(riptrm_ctx* ctx, int64_t out[5]) {
+  if (!ctx || !out) return RIPTRM_E_ARG;
+  if (!ctx->bound) return fail(ctx, RIPTRM_E_STATE, "spass_packed_info: bind first");
+  const DevParams& P = ctx->P;
+  const int64_t stored = P.layout == RIPTRM_LAYOUT_SYMTILE ? (int64_t)P.batch * P.ntiles : 0;
+  out[0] = P.spk ? 1 : 0;
+  out[1] = 0;
+  out[2] = stored;
+  out[3] = (int64_t)ctx->spk_bytes;
+  out[4] = -1;
+  if (!P.spk) return RIPTRM_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<int32_t> w((size_t)P.batch * P.spk_nfull);
+  unsigned long long mism = 0;
+  HIPCHK(ctx, hipMemcpyAsync(w.data(), ctx->spk_word, w.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(&mism, spack_mism(ctx), 8, hipMemcpyDeviceToHost, ctx->stream));
+  HIPCHK(ctx, hipStreamSynchronize(ctx->stream));
+  for (int32_t x : w) out[1] += x != 0;
+  out[2] = stored - out[1];
+  if (ctx->spk_verified) out[4] = (int64_t)mism;
+  return RIPTRM_OK;
 }
 
 int riptrm_ctx_create(riptrm_ctx** out, int device, void* stream) {
@@ -3094,6 +3357,7 @@ int riptrm_ctx_destroy(riptrm_ctx* ctx) {
     if (ctx->si) riptrm_si_release(ctx->si);
     if (ctx->gr) riptrm_gr_release(ctx->gr);
     riptrm_big_release(ctx);
+    spack_release(ctx);
     for (auto& pool : ctx->ev_pool)
       for (auto e : pool) (void)hipEventDestroy(e);
     for (auto e : {ctx->ev_fork, ctx->ev_join, ctx->ev_pass[0], ctx->ev_pass[1]})
@@ -3153,6 +3417,14 @@ int riptrm_nonnegpca_pack(riptrm_ctx* ctx, const double* Z, int64_t ldz, int64_t
   hipLaunchKernelGGL(k_pack, grid, dim3(256), 0, ctx->stream, Z, ldz, z_stride, n, S, s_stride, layout, ld,
                      rows_of(n));
   HIPCHK(ctx, hipGetLastError());
+  // packing into the bound S: its packed copy follows (same stream), so it is never stale
+  if (ctx->bound && ctx->P.spk && layout == RIPTRM_LAYOUT_SYMTILE && n == ctx->P.n &&
+      S < ctx->P.S + (int64_t)ctx->P.batch * ctx->P.inst_stride && S + (int64_t)(count - 1) * s_stride + s_elems_of(n, layout) > ctx->P.S) {
+    const int64_t d = S - ctx->P.S;
+    const bool whole = d >= 0 && d % ctx->P.inst_stride == 0 && (count == 1 || s_stride == ctx->P.inst_stride) &&
+                       d / ctx->P.inst_stride + count <= ctx->P.batch;
+    if (int rc = whole ? spack_pack(ctx, (int)(d / ctx->P.inst_stride), count) : spack_pack(ctx, 0, ctx->P.batch)) return rc;
+  }
   return RIPTRM_OK;
 }
 
@@ -3293,6 +3565,7 @@ static int persist_run(riptrm_ctx* c, int steps, int* n_active) {
   return RIPTRM_OK;
 }
 
+constexpr int SUP_MIN_UNITS = 64;   // spass_mode (below): units per instance from which kind 1 streams with k_spass_sup
 static int calibrate_spass(riptrm_ctx* c) {
   c->sup_auto = 1;
   c->spass_cal_ms[0] = c->spass_cal_ms[1] = 0.0f;
@@ -3345,6 +3618,7 @@ int riptrm_nonnegpca_bind(riptrm_ctx* ctx, const double* S, int32_t n, int32_t b
   ctx->S = S;
   ctx->inst_stride = inst_stride;
   ctx->ws = (char*)workspace;
+  spack_release(ctx);   // the previous bind's packed copy
   DevParams& P = ctx->P;
   std::memset(&P, 0, sizeof(P));
   P.S = S;
@@ -3427,6 +3701,7 @@ int riptrm_nonnegpca_bind(riptrm_ctx* ctx, const double* S, int32_t n, int32_t b
   ctx->bound = true;
   ctx->solving = false;
   ctx->pver++;
+  if (int rc = spack_build(ctx, SUP_MIN_UNITS)) return rc;
   return calibrate_spass(ctx);
 }
 
@@ -3439,7 +3714,6 @@ int riptrm_nonnegpca_bind(riptrm_ctx* ctx, const double* S, int32_t n, int32_t b
 // any batch, run after run.  Kind 3 keeps the older rule (super-tile once every CU gets a unit,
 // if the bind-time timing preferred it; fastest, not batch-independent).  The state kernel that
 // gathers the pass gets the same mode.
-constexpr int SUP_MIN_UNITS = 64;
 static int spass_mode(const riptrm_ctx* c, int bound) {
   if (c->P.layout != RIPTRM_LAYOUT_SYMTILE || c->sup_req == 0) return 0;
   if (c->sup_req == 2) return 1;

@@ -652,6 +652,13 @@ class NonnegPCABatch(DeviceBatch):
         return {"ms_per_launch_tile": t.value, "ms_per_launch_super": u.value,
                 "kernel": "k_spass_sup" if k.value == 1 else "k_spass_sym"}
 
+    def spass_packed_info(self) -> Dict[str, int]:
+        """riptrm_spass_packed_info: the packed copy of S that k_spass_sup streams (built at bind)."""
+        out = (ctypes.c_int64 * 5)()
+        self.ctx.check(self.lib.riptrm_spass_packed_info(self.ctx.h, out), "riptrm_spass_packed_info")
+        return {"in_use": bool(out[0]), "tiles_packed": int(out[1]), "tiles_plain": int(out[2]),
+                "bytes": int(out[3]), "verify_mismatches": int(out[4])}
+
     def persistent_state(self) -> Dict[str, bool]:
         """riptrm_get_persistent: whether the bound shape runs k_persist on this device, and whether
         the current solve / tCG run uses it."""

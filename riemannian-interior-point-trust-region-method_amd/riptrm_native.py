@@ -70,6 +70,12 @@ SIGNATURES: Dict[str, tuple] = {
     "riptrm_workspace_offset": (c_int64, [c_int32, c_int32, c_int32, c_int32, c_int32]),
     "riptrm_sup_unit_bytes": (c_int64, [c_int32, c_int32]),
     "riptrm_sup_deal": (c_int64, [c_int32, c_int32, c_int32, c_int32, P_int32, P_int32, P_int32, c_int64]),
+    "riptrm_spack_pass_bytes": (c_int64, [c_int32]),
+    "riptrm_spack_tile_bytes": (c_int32, []),
+    "riptrm_spack_classify": (c_int32, [c_void_p, c_int64, P_int32]),
+    "riptrm_spack_encode_block": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "riptrm_spack_decode_block": (c_int32, [c_void_p, c_int32, c_void_p]),
+    "riptrm_spass_packed_info": (c_int32, [c_void_p, ctypes.POINTER(c_int64)]),
     "riptrm_nonnegpca_pack": (c_int32, [c_void_p, c_void_p, c_int64, c_int64, c_int32, c_int32, c_void_p,
                                         c_int32, c_int64]),
     "riptrm_nonnegpca_bind": (c_int32, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64,
