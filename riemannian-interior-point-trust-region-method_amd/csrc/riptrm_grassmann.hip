@@ -41,10 +41,12 @@
 // solver of riptrm_trs.h; with second_order_stationarity the same matrix at the trial point gives
 // mineigvalHw.  The tCG kernels k_gr are compiled as they were (DESIGN.md 7e has the resource table).
 #include <hip/hip_runtime.h>
+#include <float.h>
 #include <math.h>
 #include <cstring>
 #include <string>
 #include "riptrm_ctx.h"
+#include "riptrm_rules.h"
 #include "riptrm_wave.h"
 #include "riptrm_trs.h"
 #include "riptrm_grassmann_ops.h"
@@ -54,8 +56,8 @@ namespace riptrm_gr {
 #pragma clang fp contract(off)
 
 using namespace riptrm_gr_dev;
-using riptrm::np_max;
-using riptrm::np_min;
+namespace rules = riptrm::rules;
+using rules::Info;
 using riptrm::round_up;
 
 constexpr int NKMAX = RIPTRM_GR_NKMAX;
@@ -135,10 +137,6 @@ constexpr int exact_dim_max() {
 constexpr int EXACT_DMAX = exact_dim_max();
 static_assert(EXACT_DMAX >= 80, "every shape with k (n - k) <= 80 must fit");
 
-struct Info {  // inner-iteration record of solver_status (RIPTRM.py:986-1023)
-  double has, num, status, tr, dxtype, normdx, minx, miny, compl_, hasratio, ratio, ru, dc;
-};
-
 template <int NT, bool TRAIL, bool EXACT = false>
 struct Eng : Ops {
   const GRParams& P;
@@ -148,10 +146,9 @@ struct Eng : Ops {
   lf *SIG;                 // KMAX singular values
   riptrm_trs::Blk<NT> blk;
   // EXACT only: the frame (Ops' REF = R, BETA and CW), the frame vector FV = DEL and its image
-  // FH = HETA, the subproblem's work area, the row's mineigvalHw
+  // FH = HETA, the subproblem's work area
   lf *FV, *FH;
   double* trs_lds;
-  double so_has = 0.0, so_min = 0.0;
 
   __device__ __forceinline__ Eng(const GRParams& P_, int b_, double* lds)
       : Ops(P_.n, P_.k), P(P_), b(b_), blk(lds + NVEC * NT + 4 * KK + KMAX) {
@@ -285,7 +282,7 @@ struct Eng : Ops {
     jacobi(W2, n, false);
     double smax = 0.0;
     for (int j = 0; j < k; ++j) smax = fmax(smax, SIG[j]);
-    const double tol = smax * (double)(n > k ? n : k) * 2.220446049250313e-16;
+    const double tol = smax * (double)(n > k ? n : k) * DBL_EPSILON;   // numpy's finfo(float64).eps
     int rank = 0;
     for (int j = 0; j < k; ++j) rank += (SIG[j] > tol) ? 1 : 0;
     return rank == k;
@@ -327,8 +324,6 @@ struct Eng : Ops {
 
   // ---- tCG, RIPTRM.py:41-216 (eta0 = 0, identity preconditioner); eta / Heta in ETA / HETA -------
   __device__ __forceinline__ int tcg(double Delta, int& jout, double& hvps) {
-    const double theta = P.opt.tcg_theta, kappa = P.opt.tcg_kappa;
-    const int mininner = P.opt.tcg_mininner;
     const int maxinner = k * (n - k);   // manifold.dim
     ETA[l] = 0.0;
     HETA[l] = 0.0;
@@ -345,6 +340,7 @@ struct Eng : Ops {
     double model = 0.0;
     int stop = RIPTRM_TCG_MAX_INNER_ITER;
     int j = 0;
+    const double nr0t = pow(norm_r0, P.opt.tcg_theta);   // constant over the run
     for (j = 0; j < maxinner; ++j) {
       hw(HD, DEL);
       hvps += 1.0;
@@ -353,23 +349,17 @@ struct Eng : Ops {
         stop = RIPTRM_TCG_NONFINITE;
         break;
       }
-      double al = 0.0, e_Pe_new;
-      if (d_Hd != 0.0) {
-        al = z_r / d_Hd;
-        e_Pe_new = (e_Pe + 2.0 * al * e_Pd) + (al * al) * d_Pd;
-      } else {
-        e_Pe_new = e_Pe;
-      }
-      const double D2 = Delta * Delta;
-      if (d_Hd <= 0.0 || e_Pe_new >= D2) {
-        const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (D2 - e_Pe))) / d_Pd;
-        ETA[l] = ETA[l] + tau * DEL[l];
-        HETA[l] = HETA[l] + tau * HD[l];
+      const rules::Curvature cv = rules::tcg_curvature(d_Hd, z_r, e_Pd, d_Pd, e_Pe, Delta);
+      const double al = cv.alpha;
+      if (cv.boundary) {
+        const rules::Boundary bd = rules::tcg_boundary(d_Hd, e_Pd, d_Pd, e_Pe, Delta);
+        ETA[l] = ETA[l] + bd.tau * DEL[l];
+        HETA[l] = HETA[l] + bd.tau * HD[l];
         __syncthreads();
-        stop = d_Hd <= 0.0 ? RIPTRM_TCG_NEGATIVE_CURVATURE : RIPTRM_TCG_EXCEEDED_TR;
+        stop = bd.stop;
         break;
       }
-      e_Pe = e_Pe_new;
+      e_Pe = cv.e_Pe_new;
       const double ne = ETA[l] + al * DEL[l];
       const double nh = HETA[l] + al * HD[l];
       const double cl = act ? C[l] : 0.0;
@@ -385,22 +375,24 @@ struct Eng : Ops {
       R[l] = rn;
       r_r = bsum(act ? rn * rn : 0.0);
       norm_r = sqrt(r_r);
-      if (j >= mininner && norm_r <= norm_r0 * fmin(pow(norm_r0, theta), kappa)) {
+      const int target = rules::tcg_target((double)j, P.opt.tcg_mininner, norm_r, norm_r0, nr0t, P.opt.tcg_kappa);
+      if (target != rules::TCG_CONTINUE) {
         __syncthreads();
-        stop = kappa < pow(norm_r0, theta) ? RIPTRM_TCG_REACHED_TARGET_LINEAR : RIPTRM_TCG_REACHED_TARGET_SUPERLINEAR;
+        stop = target;
         break;
       }
-      const double zold = z_r;
-      z_r = r_r;   // z = r: <z, r> is <r, r>
-      const double beta = z_r / zold;
+      const double beta = rules::tcg_beta(r_r, z_r);
       DEL[l] = -rn + beta * DEL[l];
       __syncthreads();
       proj_to(DEL, X, DEL);
-      e_Pd = beta * (e_Pd + al * d_Pd);
-      d_Pd = z_r + (beta * beta) * d_Pd;
+      const rules::Advance av = rules::tcg_advance((double)j, maxinner, beta, r_r, e_Pd, d_Pd, al);
+      z_r = av.z_r;
+      e_Pd = av.e_Pd;
+      d_Pd = av.d_Pd;
+      if (av.stop != rules::TCG_CONTINUE) break;   // stop is RIPTRM_TCG_MAX_INNER_ITER already; j stays
     }
     __syncthreads();
-    if (j >= maxinner) j = maxinner - 1;  // Python's range loop variable after exhaustion
+    if (j >= maxinner) j = maxinner - 1;  // maxinner = 0 only (op_tcg): no iteration ran, j = -1
     jout = j;
     return stop;
   }
@@ -522,8 +514,8 @@ struct Eng : Ops {
     return bmax(t);
   }
 
-  __device__ __forceinline__ void log_row(const double (&ev)[10], double outer_it, double mu, const Info* inf,
-                                          double tcg_iters, double t_now, double t_start, double& count, double& overflow) {
+  __device__ __forceinline__ void log_row(const double (&ev)[10], double outer_it, double mu, const Info& inf,
+                                          bool has_info, double tcg_iters, double t_now, double t_start, double& count, double& overflow) {
     if constexpr (TRAIL) {   // the evaluated point into the record's own slot (X, Y are what evaluation() read)
       const int64_t capt = P.opt.log_capacity < P.cap ? P.opt.log_capacity : P.cap;
       if (capt > 0 && act) {
@@ -538,41 +530,8 @@ struct Eng : Ops {
       if (capl > 0) {
         if (cnt >= capl) overflow += 1.0;   // a record leaves the middle of the log (head + latest kept)
         double* L = P.log + ((int64_t)b * P.cap + riptrm::log_slot(cnt, capl)) * RIPTRM_LOG_NFIELDS;
-        for (int q = 0; q < RIPTRM_LOG_NFIELDS; ++q) L[q] = 0.0;
-        L[RIPTRM_LOG_ITERATION] = outer_it;
-        L[RIPTRM_LOG_TIME] = (cnt == 0) ? 0.0 : (t_now - t_start) / P.clock_hz;
-        L[RIPTRM_LOG_COST] = ev[0];
-        L[RIPTRM_LOG_DISTANCE] = ev[1];
-        L[RIPTRM_LOG_RESIDUAL] = ev[2];
-        L[RIPTRM_LOG_GRADNORM] = ev[3];
-        L[RIPTRM_LOG_COMPLVIOLATION] = ev[4];
-        L[RIPTRM_LOG_DUALVIOLATION] = ev[5];
-        L[RIPTRM_LOG_MANVIOLATION] = ev[6];
-        L[RIPTRM_LOG_MAXVIOLATION] = ev[7];
-        L[RIPTRM_LOG_MEANVIOLATION] = ev[8];
-        L[RIPTRM_LOG_MU] = mu;
-        L[RIPTRM_LOG_MAXABSLAGMULT] = ev[9];
-        L[RIPTRM_LOG_TCG_ITERS] = tcg_iters;
-        L[RIPTRM_LOG_DUAL_CLIPPING] = -1.0;
-        if (inf) {
-          L[RIPTRM_LOG_HAS_INFO] = inf->has;
-          L[RIPTRM_LOG_NUM_INNER] = inf->num;
-          L[RIPTRM_LOG_INNER_STATUS] = inf->status;
-          L[RIPTRM_LOG_TR_RADIUS] = inf->tr;
-          L[RIPTRM_LOG_DXTYPE] = inf->dxtype;
-          L[RIPTRM_LOG_NORMDX] = inf->normdx;
-          L[RIPTRM_LOG_MINXFEASI] = inf->minx;
-          L[RIPTRM_LOG_MINYFEASI] = inf->miny;
-          L[RIPTRM_LOG_COMPL] = inf->compl_;
-          L[RIPTRM_LOG_HAS_RATIO] = inf->hasratio;
-          L[RIPTRM_LOG_ARED_PRED] = inf->ratio;
-          L[RIPTRM_LOG_RADIUS_UPDATE] = inf->ru;
-          L[RIPTRM_LOG_DUAL_CLIPPING] = inf->dc;
-          if constexpr (EXACT) {
-            L[RIPTRM_LOG_HAS_MINEIG] = so_has;
-            L[RIPTRM_LOG_MINEIGVALHW] = so_min;
-          }
-        }
+        rules::write_log_row(L, rules::ROW_BLANK, outer_it, rules::log_time(cnt == 0, t_now, t_start, P.clock_hz), ev, mu,
+                             tcg_iters, inf, has_info, EXACT);
       } else {
         overflow += 1.0;
       }
@@ -580,10 +539,7 @@ struct Eng : Ops {
     count += 1.0;
   }
 
-  __device__ __forceinline__ double mu_at(int idx) const {
-    const int i = idx < P.tab_len ? idx : P.tab_len - 1;
-    return P.mu_tab[i];
-  }
+  __device__ __forceinline__ double mu_at(int idx) const { return P.mu_tab[rules::tab_index(idx, P.tab_len)]; }
   __device__ __forceinline__ double load(const double* base) const { return act ? base[(int64_t)b * N + l] : 0.0; }
   __device__ __forceinline__ void store(double* base, double v) const {
     if (act) base[(int64_t)b * N + l] = v;
@@ -615,8 +571,7 @@ struct Eng : Ops {
       evaluation(xHead, ev);
       double tn = now();
       if (outer_it == 0.0 || !save_inner)
-        log_row(ev, outer_it, mu, (outer_it != 0.0 && have_info) ? &info : nullptr, last_j + 1.0, tn, t_start,
-                log_count, log_over);
+        log_row(ev, outer_it, mu, info, outer_it != 0.0 && have_info, last_j + 1.0, tn, t_start, log_count, log_over);
       residual = ev[2];
       xHead = act ? X[l] : 0.0;
       const double rt = (tn - t_start) / P.clock_hz;
@@ -629,18 +584,14 @@ struct Eng : Ops {
         stop_rt = rt;
         break;
       }
-      int stop = RIPTRM_STOP_NONE;
-      if (rt >= P.opt.maxtime) stop = RIPTRM_STOP_MAXTIME;
-      else if (outer_it >= (double)P.opt.maxiter) stop = RIPTRM_STOP_MAXITER;
-      if (ev[2] <= P.opt.tolresid) stop = RIPTRM_STOP_TOLRESID;
+      const int stop = rules::outer_stop(rt, outer_it, ev[2], P.opt);
       if (stop != RIPTRM_STOP_NONE) {
         stop_code = stop;
         stop_rt = rt;
         break;
       }
       // restart_every cycling (benchmark windows)
-      const int re = P.opt.restart_every;
-      if (re > 0 && outer_it > 0.0 && fmod(outer_it, (double)re) == 0.0) {
+      if (rules::restart_due(outer_it, P.opt)) {
         set_point(xI, yI);
         mu_idx = 0.0;
         mu = mu_at(0);
@@ -653,7 +604,7 @@ struct Eng : Ops {
       xPrev = x0;
       inner_it = 0.0;
       t_inner = now();
-      const int ti = (int)mu_idx < P.tab_len ? (int)mu_idx : P.tab_len - 1;
+      const int ti = rules::tab_index((int)mu_idx, P.tab_len);
       const double tolL = P.tolL_tab[ti], tolC = P.tolC_tab[ti];
       while (true) {  // inner_run, RIPTRM.py:785-847
         inner_it += 1.0;
@@ -700,12 +651,11 @@ struct Eng : Ops {
         const bool yfeas = bmin(act ? (yN > 0.0 ? 1.0 : 0.0) : 1.0) > 0.0;
         const double cvv = act ? yN * sN - mu : 0.0;
         const double compl_ = sqrt(bsum(cvv * cvv));
-        info = Info{1.0, inner_it, 0.0, DeltaStep, (double)tstop, normdx, minx, miny, compl_, 0.0, 0.0, 0.0, -1.0};
+        info = Info{1.0, inner_it, 0.0, DeltaStep, (double)tstop, normdx, minx, miny, compl_, 0.0, 0.0, 0.0, -1.0,
+                    0.0, 0.0};
         have_info = true;
         bool mineig_ok = true;
         if constexpr (EXACT) {
-          so_has = 0.0;
-          so_min = 0.0;
           if (P.opt.second_order_stationarity) {   // RIPTRM.py:599-613: HwNew's matrix at (xNew, yNew)
             // recomputed at the next step where the reference reuses HwNewmatrix (:687-692): the frame is
             // deterministic, so the two are equal.  The operators move to the trial point and back
@@ -720,10 +670,9 @@ struct Eng : Ops {
               err = code;
               break;
             }
-            const double tol2 = P.opt.tol2_table ? P.opt.tol2_table[ti] : mu;
-            mineig_ok = me >= -tol2;
-            so_has = 1.0;
-            so_min = me;
+            mineig_ok = me >= -rules::tol2(P.opt, ti, mu);
+            info.hasmin = 1.0;
+            info.mineig = me;
           }
         }
         bool converged = false;
@@ -747,38 +696,20 @@ struct Eng : Ops {
           hw(HD, ETA);
           hvps += 1.0;
           double pred = (0.0 - 0.5 * dot(HD, ETA)) - dot(C, ETA);
-          const double red_reg = fmax(1.0, fabs(lb_c)) * 2.220446049250313e-16 * P.opt.reduction_regularization;
+          const double red_reg = rules::red_reg(lb_c, P.opt);
           ared = ared + red_reg;
           pred = pred + red_reg;
           if (!isfinite(ared) || !isfinite(pred)) {
             err = RIPTRM_ERR_NONFINITE;
             break;
           }
-          const double ratio = ared / pred;
-          double Dn;
-          int ru;
-          if (ared < 0.25 * pred) {
-            ru = RIPTRM_RU_REDUCED;
-            Dn = 0.25 * Delta;
-          } else if (ared >= 0.75 * pred && fabs(normdx - Delta) <= 1e-15) {
-            ru = RIPTRM_RU_EXPANDED;
-            const double d2 = 2.0 * Delta;
-            Dn = d2 < P.opt.maximal_tr_radius ? d2 : P.opt.maximal_tr_radius;
-          } else {
-            ru = RIPTRM_RU_UNCHANGED;
-            Dn = Delta;
-          }
+          const rules::Radius ra = rules::radius_update(ared, pred, normdx, Delta, P.opt);
           info.hasratio = 1.0;
-          info.ratio = ratio;
-          info.ru = ru;
-          if (ared > P.opt.rho * pred) {
-            const double cl = P.opt.const_left, crr = P.opt.const_right;
-            const double iright = np_max(crr, crr / mu);   // RIPTRM.py:682 (3-arg np.maximum quirk)
-            double yc = 0.0;
-            if (act) {
-              const double il = cl * np_min(np_min(y, mu / sN), 1.0);
-              yc = np_min(np_max(yN, il), iright);
-            }
+          info.ratio = ared / pred;
+          info.ru = ra.ru;
+          if (rules::accepted(ared, pred, P.opt)) {
+            const double iright = rules::clip_right(mu, P.opt);
+            const double yc = act ? rules::clip_dual(y, yN, sN, mu, iright, P.opt) : 0.0;
             const double nd = bsum((act && yc != yN) ? 1.0 : 0.0);
             set_point(xN, yc);
             info.status = RIPTRM_IS_SUCCESSFUL;
@@ -786,29 +717,20 @@ struct Eng : Ops {
           } else {
             info.status = RIPTRM_IS_UNSUCCESSFUL;
           }
-          Delta = Dn;
+          Delta = ra.Dn;
         }
         // inner_run tail, RIPTRM.py:810-847
         inner_total += 1.0;
         tn = now();
         if (save_inner) {
           evaluation(xPrev, ev);
-          log_row(ev, outer_it, mu, &info, last_j + 1.0, tn, t_start, log_count, log_over);
+          log_row(ev, outer_it, mu, info, true, last_j + 1.0, tn, t_start, log_count, log_over);
         }
         xPrev = act ? X[l] : 0.0;
         bool exitflag = converged;
-        double rti, lim;
-        if (P.opt.inner_maxtime < 0.0) {
-          lim = P.opt.maxtime;
-          rti = (tn - t_start) / P.clock_hz;
-        } else {
-          lim = P.opt.inner_maxtime;
-          rti = (tn - t_inner) / P.clock_hz;
-        }
-        const bool tmo = rti >= lim;
-        const bool imax = P.opt.inner_maxiter >= 0 && inner_it >= (double)P.opt.inner_maxiter;
-        if (tmo || imax) {
-          info.status = imax ? RIPTRM_IS_MAX_ITER_EXCEEDED : RIPTRM_IS_MAX_TIME_EXCEEDED;
+        const int limit = rules::inner_limit(tn, t_start, t_inner, P.clock_hz, inner_it, P.opt);
+        if (limit != 0) {
+          info.status = limit;
           exitflag = true;
           set_point(x0, y0);
           xPrev = x0;
@@ -822,31 +744,16 @@ struct Eng : Ops {
         break;
       }
       // outer_step tail, RIPTRM.py:889-896
-      mu_idx += 1.0;
+      rules::outer_tail(mu_idx, Delta, P.opt);
       mu = mu_at((int)mu_idx);
-      const double mn = P.opt.minimal_initial_tr_radius;
-      Delta = Delta > mn ? Delta : mn;
     }
     store(P.x, act ? X[l] : 0.0);
     store(P.y, act ? Y[l] : 0.0);
     if (l == 0) {
-      double* o = P.stats + (int64_t)b * RIPTRM_STAT_NFIELDS;
-      for (int q = 0; q < RIPTRM_STAT_NFIELDS; ++q) o[q] = 0.0;
-      o[RIPTRM_STAT_OUTER_ITERS] = outer_it;
-      o[RIPTRM_STAT_INNER_ITERS] = inner_total;
-      o[RIPTRM_STAT_TCG_ITERS] = tcg_total;
-      o[RIPTRM_STAT_PASSES] = hvps;
-      o[RIPTRM_STAT_STOP_CODE] = stop_code;
-      o[RIPTRM_STAT_STOP_RUNTIME] = stop_rt;
-      o[RIPTRM_STAT_FINAL_RESIDUAL] = residual;
-      o[RIPTRM_STAT_LOG_COUNT] = log_count;
-      o[RIPTRM_STAT_LOG_OVERFLOW] = log_over;
-      o[RIPTRM_STAT_PHASE] = err != RIPTRM_ERR_NONE ? riptrm::PH_ERROR : riptrm::PH_DONE;
-      o[RIPTRM_STAT_ERROR] = err;
-      o[RIPTRM_STAT_MU] = mu;
-      o[RIPTRM_STAT_TR_RADIUS] = Delta;
-      o[RIPTRM_STAT_TCG_LAST_J] = last_j;
-      o[RIPTRM_STAT_TCG_LAST_STOP] = last_stop;
+      const double phase = err != RIPTRM_ERR_NONE ? riptrm::PH_ERROR : riptrm::PH_DONE;
+      rules::write_stats(P.stats + (int64_t)b * RIPTRM_STAT_NFIELDS, true,
+                         rules::Stats{outer_it, inner_total, tcg_total, hvps, stop_code, stop_rt, residual, log_count,
+                                      log_over, phase, (double)err, mu, Delta, last_j, last_stop});
     }
   }
 

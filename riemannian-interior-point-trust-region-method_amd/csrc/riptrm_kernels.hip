@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <type_traits>
 #include "riptrm_device.h"
+#include "riptrm_rules.h"
 #include "riptrm_spack.h"
 #include "riptrm_ctx.h"
 #include "riptrm_wave.h"
@@ -1112,12 +1113,13 @@ struct RepBlock {
 // TCG_CONTINUE (d is the next direction, j advanced) or the stop code (eta / Heta final, j as the
 // reference leaves it).  The hooks load late operands / store results for the workspace-backed
 // caller (k_state); the persistent fast path passes no-ops and keeps everything in registers.  One
-// body for both, so the two paths are bitwise identical.
+// body for both, so the two paths are bitwise identical.  Its scalar rules are an inline copy of the
+// tCG functions of riptrm_rules.h, kept for the lean path's speed (see there); change both together.
 struct TcgScalars {
   double coef, z_r, e_Pd, d_Pd, e_Pe, Delta, model, nr0, j;
   double nr0t;   // pow(nr0, tCG_theta): constant over a tCG run (RIPTRM.py:180-182), computed once
 };
-constexpr int TCG_CONTINUE = -1;
+using rules::TCG_CONTINUE;
 
 // The part of the barrier-Hessian action that does not need u = S delta: xv = <x, delta>,
 // q = y (delta - x xv) / x and xq = <x, q> (the lean path computes it while the S-pass's partial
@@ -1326,10 +1328,7 @@ struct MachineT {
 
   __device__ __forceinline__ double* V(int k) const { return vbase + k * vkstride; }
   __device__ __forceinline__ double elapsed_u(double t0) { return (unow() - t0) / P.clock_hz; }
-  __device__ __forceinline__ double mu_at(int idx) const {
-    const int i = idx < P.tab_len ? idx : P.tab_len - 1;
-    return P.mu_tab[i];
-  }
+  __device__ __forceinline__ double mu_at(int idx) const { return P.mu_tab[rules::tab_index(idx, P.tab_len)]; }
 
   __device__ __forceinline__ void copy(int dst, int src) {
     double* d = V(dst);
@@ -1415,24 +1414,13 @@ struct MachineT {
       double* g = cold;
 #pragma unroll
       for (int k = 0; k < ST_HOT; ++k) g[k] = s[k];
-      double* o = ostats;
-      o[RIPTRM_STAT_OUTER_ITERS] = s[ST_OUTER_IT];
-      o[RIPTRM_STAT_INNER_ITERS] = g[ST_INNER_TOTAL];
-      o[RIPTRM_STAT_TCG_ITERS] = g[ST_TCG_TOTAL];
-      o[RIPTRM_STAT_PASSES] = g[ST_PASSES];
-      o[RIPTRM_STAT_RHS] = g[ST_RHS];
-      o[RIPTRM_STAT_STOP_CODE] = g[ST_STOP_CODE];
-      o[RIPTRM_STAT_STOP_RUNTIME] = g[ST_STOP_RUNTIME];
-      o[RIPTRM_STAT_FINAL_RESIDUAL] = g[ST_RESIDUAL];
-      o[RIPTRM_STAT_LOG_COUNT] = g[ST_LOG_COUNT];
-      o[RIPTRM_STAT_LOG_OVERFLOW] = g[ST_LOG_OVERFLOW];
-      o[RIPTRM_STAT_PHASE] = s[ST_PHASE];
-      o[RIPTRM_STAT_MU] = s[ST_MU];
-      o[RIPTRM_STAT_TR_RADIUS] = s[ST_DELTA];
-      o[RIPTRM_STAT_TCG_LAST_J] = s[ST_J];
-      o[RIPTRM_STAT_TCG_LAST_STOP] = s[ST_TCG_STOP];
-      o[RIPTRM_STAT_ERROR] = g[ST_ERROR];
-      o[RIPTRM_STAT_LOG_BASE] = g[ST_LOG_BASE];
+      // this engine does not zero the block, and RHS / LOG_BASE are its own fields (riptrm_rules.h)
+      rules::write_stats(ostats, false,
+                         rules::Stats{s[ST_OUTER_IT], g[ST_INNER_TOTAL], g[ST_TCG_TOTAL], g[ST_PASSES], g[ST_STOP_CODE],
+                                      g[ST_STOP_RUNTIME], g[ST_RESIDUAL], g[ST_LOG_COUNT], g[ST_LOG_OVERFLOW], s[ST_PHASE],
+                                      g[ST_ERROR], s[ST_MU], s[ST_DELTA], s[ST_J], s[ST_TCG_STOP]});
+      ostats[RIPTRM_STAT_RHS] = g[ST_RHS];
+      ostats[RIPTRM_STAT_LOG_BASE] = g[ST_LOG_BASE];
     }
   }
 
@@ -1535,36 +1523,13 @@ struct MachineT {
       const int64_t capl = P.opt.log_capacity < ocap ? P.opt.log_capacity : ocap;
       if (capl > 0) {
         if (k >= capl) cold[ST_LOG_OVERFLOW] += 1.0;   // a record leaves the middle of the log
-        double* L = olog + log_slot(k, capl) * RIPTRM_LOG_NFIELDS;
-        L[RIPTRM_LOG_ITERATION] = s[ST_OUTER_IT];
-        L[RIPTRM_LOG_TIME] = (cnt == 0) ? 0.0 : (t_now - s[ST_T_START]) / P.clock_hz;
-        L[RIPTRM_LOG_COST] = ev[0];
-        L[RIPTRM_LOG_DISTANCE] = ev[1];
-        L[RIPTRM_LOG_RESIDUAL] = ev[2];
-        L[RIPTRM_LOG_GRADNORM] = ev[3];
-        L[RIPTRM_LOG_COMPLVIOLATION] = ev[4];
-        L[RIPTRM_LOG_DUALVIOLATION] = ev[5];
-        L[RIPTRM_LOG_MANVIOLATION] = ev[6];
-        L[RIPTRM_LOG_MAXVIOLATION] = ev[7];
-        L[RIPTRM_LOG_MEANVIOLATION] = ev[8];
-        L[RIPTRM_LOG_MU] = s[ST_MU];
-        L[RIPTRM_LOG_HAS_INFO] = info ? c[ST_I_HAS] : 0.0;
-        L[RIPTRM_LOG_NUM_INNER] = c[ST_I_NUM];
-        L[RIPTRM_LOG_INNER_STATUS] = c[ST_I_STATUS];
-        L[RIPTRM_LOG_TR_RADIUS] = c[ST_I_TR];
-        L[RIPTRM_LOG_DXTYPE] = c[ST_I_DXTYPE];
-        L[RIPTRM_LOG_NORMDX] = c[ST_I_NORMDX];
-        L[RIPTRM_LOG_MINXFEASI] = c[ST_I_MINX];
-        L[RIPTRM_LOG_MINYFEASI] = c[ST_I_MINY];
-        L[RIPTRM_LOG_COMPL] = c[ST_I_COMPL];
-        L[RIPTRM_LOG_HAS_RATIO] = c[ST_I_HASRATIO];
-        L[RIPTRM_LOG_ARED_PRED] = c[ST_I_RATIO];
-        L[RIPTRM_LOG_RADIUS_UPDATE] = c[ST_I_RU];
-        L[RIPTRM_LOG_DUAL_CLIPPING] = c[ST_I_DC];
-        L[RIPTRM_LOG_HAS_MINEIG] = c[ST_I_HASMIN];
-        L[RIPTRM_LOG_MINEIGVALHW] = c[ST_I_MINEIG];
-        L[RIPTRM_LOG_MAXABSLAGMULT] = ev[9];
-        L[RIPTRM_LOG_TCG_ITERS] = s[ST_J] + 1.0;
+        // the last inner_info lives in the cold slots; a row without info repeats it with HAS_INFO = 0
+        const rules::Info inf{c[ST_I_HAS], c[ST_I_NUM], c[ST_I_STATUS], c[ST_I_TR], c[ST_I_DXTYPE],
+                              c[ST_I_NORMDX], c[ST_I_MINX], c[ST_I_MINY], c[ST_I_COMPL], c[ST_I_HASRATIO],
+                              c[ST_I_RATIO], c[ST_I_RU], c[ST_I_DC], c[ST_I_HASMIN], c[ST_I_MINEIG]};
+        rules::write_log_row(olog + log_slot(k, capl) * RIPTRM_LOG_NFIELDS, rules::ROW_KEEP, s[ST_OUTER_IT],
+                             rules::log_time(cnt == 0, t_now, s[ST_T_START], P.clock_hz), ev, s[ST_MU], s[ST_J] + 1.0,
+                             inf, info, true);
       } else {
         cold[ST_LOG_OVERFLOW] += 1.0;
       }
@@ -1602,10 +1567,7 @@ struct MachineT {
     cset(ST_RESIDUAL, ev[2]);
     if (!isfinite(ev[2])) return nonfinite_stop(false);   // deliberate deviation, include/riptrm.h
     const double rt = (tn - s[ST_T_START]) / P.clock_hz;
-    int stop = RIPTRM_STOP_NONE;
-    if (rt >= P.opt.maxtime) stop = RIPTRM_STOP_MAXTIME;
-    else if (s[ST_OUTER_IT] >= (double)P.opt.maxiter) stop = RIPTRM_STOP_MAXITER;
-    if (ev[2] <= P.opt.tolresid) stop = RIPTRM_STOP_TOLRESID;
+    const int stop = rules::outer_stop(rt, s[ST_OUTER_IT], ev[2], P.opt);
     if (stop != RIPTRM_STOP_NONE) {
       cset(ST_STOP_CODE, stop);
       cset(ST_STOP_RUNTIME, rt);
@@ -1621,8 +1583,7 @@ struct MachineT {
 
   // restart_every cycling (benchmark windows only): back to (x0, y0, mu_0, Delta_0)
   __device__ __forceinline__ void maybe_restart() {
-    const int k = P.opt.restart_every;
-    if (k > 0 && s[ST_OUTER_IT] > 0.0 && fmod(s[ST_OUTER_IT], (double)k) == 0.0) {
+    if (rules::restart_due(s[ST_OUTER_IT], P.opt)) {
       copy(V_X, V_XI);
       copy(V_Y, V_YI);
       copy(V_SX, V_SXI);
@@ -1636,8 +1597,7 @@ struct MachineT {
   __device__ __forceinline__ int start_outer_step() {
     maybe_restart();
     s[ST_OUTER_IT] += 1.0;
-    const int mi = (int)s[ST_MU_IDX];
-    const int ti = mi < P.tab_len ? mi : P.tab_len - 1;
+    const int ti = rules::tab_index((int)s[ST_MU_IDX], P.tab_len);
     s[ST_TOLL] = P.tolL_tab[ti];
     s[ST_TOLC] = P.tolC_tab[ti];
     copy(V_X0, V_X);
@@ -1749,27 +1709,19 @@ struct MachineT {
       s[ST_TCG_STOP] = RIPTRM_TCG_NONFINITE;
       return tcg_end();
     }
-    const double z_r = s[ST_ZR], e_Pd = s[ST_EPD], d_Pd = s[ST_DPD], e_Pe = s[ST_EPE];
-    const double Delta = s[ST_DELTA];
-    double alpha = 0.0, e_Pe_new;
-    if (d_Hd != 0.0) {
-      alpha = z_r / d_Hd;
-      e_Pe_new = (e_Pe + 2.0 * alpha * e_Pd) + (alpha * alpha) * d_Pd;
-    } else {
-      e_Pe_new = e_Pe;
-    }
-    const double D2 = Delta * Delta;
-    if (d_Hd <= 0.0 || e_Pe_new >= D2) {
-      const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (D2 - e_Pe))) / d_Pd;
+    const rules::Curvature cv = rules::tcg_curvature(d_Hd, s[ST_ZR], s[ST_EPD], s[ST_DPD], s[ST_EPE], s[ST_DELTA]);
+    const double alpha = cv.alpha;
+    if (cv.boundary) {
+      const rules::Boundary bd = rules::tcg_boundary(d_Hd, s[ST_EPD], s[ST_DPD], s[ST_EPE], s[ST_DELTA]);
       #pragma unroll 4
       for (int i = tid; i < n; i += ST_THREADS) {
-        E[i] = E[i] + tau * D[i];
-        HE[i] = HE[i] + tau * U[i];
+        E[i] = E[i] + bd.tau * D[i];
+        HE[i] = HE[i] + bd.tau * U[i];
       }
-      s[ST_TCG_STOP] = d_Hd <= 0.0 ? RIPTRM_TCG_NEGATIVE_CURVATURE : RIPTRM_TCG_EXCEEDED_TR;
+      s[ST_TCG_STOP] = bd.stop;
       return tcg_end();
     }
-    s[ST_EPE] = e_Pe_new;
+    s[ST_EPE] = cv.e_Pe_new;
     double m2[2] = {0.0, 0.0};
     #pragma unroll 4
     for (int i = tid; i < n; i += ST_THREADS) {
@@ -1796,18 +1748,14 @@ struct MachineT {
     }
     bsum<1>(R, r2);
     const double r_r = r2[0];
-    const double norm_r = sqrt(r_r);
     const double nr0 = s[ST_NORMR0];
-    const double th = P.opt.tcg_theta, ka = P.opt.tcg_kappa;
-    const double nr0t = pow(nr0, th);
-    const double j = s[ST_J];
-    if (j >= (double)P.opt.tcg_mininner && norm_r <= nr0 * fmin(nr0t, ka)) {
-      s[ST_TCG_STOP] = ka < nr0t ? RIPTRM_TCG_REACHED_TARGET_LINEAR : RIPTRM_TCG_REACHED_TARGET_SUPERLINEAR;
+    const int target = rules::tcg_target(s[ST_J], P.opt.tcg_mininner, sqrt(r_r), nr0, pow(nr0, P.opt.tcg_theta),
+                                         P.opt.tcg_kappa);
+    if (target != TCG_CONTINUE) {
+      s[ST_TCG_STOP] = target;
       return tcg_end();
     }
-    const double zold = z_r;
-    const double znew = r_r;
-    const double beta = znew / zold;
+    const double beta = rules::tcg_beta(r_r, s[ST_ZR]);
     double p1[1] = {0.0};
     #pragma unroll 4
     for (int i = tid; i < n; i += ST_THREADS) {
@@ -1819,13 +1767,13 @@ struct MachineT {
     const double xd = p1[0];
     #pragma unroll 4
     for (int i = tid; i < n; i += ST_THREADS) Dw[i] = Dw[i] - xd * X[i];  // to_tangent_space
-    s[ST_ZR] = znew;
-    s[ST_EPD] = beta * (e_Pd + alpha * d_Pd);
-    s[ST_DPD] = znew + (beta * beta) * d_Pd;
-    s[ST_J] = j + 1.0;
-    if (j + 1.0 >= (double)(n - 1)) {  // range(maxinner) exhausted; Python j stays maxinner-1
-      s[ST_J] = j;
-      s[ST_TCG_STOP] = RIPTRM_TCG_MAX_INNER_ITER;
+    const rules::Advance av = rules::tcg_advance(s[ST_J], n - 1, beta, r_r, s[ST_EPD], s[ST_DPD], alpha);
+    s[ST_ZR] = av.z_r;
+    s[ST_EPD] = av.e_Pd;
+    s[ST_DPD] = av.d_Pd;
+    s[ST_J] = av.j;
+    if (av.stop != TCG_CONTINUE) {   // maxinner = manifold.dim = n - 1
+      s[ST_TCG_STOP] = av.stop;
       return tcg_end();
     }
     return request(1);
@@ -2154,8 +2102,7 @@ struct MachineT {
 
   // s[ST_MINEIG] against -forcing_function_second_order(mu) (RIPTRM.py:613)
   __device__ __forceinline__ void mineig_test() {
-    const int mi = (int)s[ST_MU_IDX];
-    const double tol2 = P.opt.tol2_table ? P.opt.tol2_table[mi < P.tab_len ? mi : P.tab_len - 1] : s[ST_MU];
+    const double tol2 = rules::tol2(P.opt, rules::tab_index((int)s[ST_MU_IDX], P.tab_len), s[ST_MU]);
     s[ST_HASMIN] = 1.0;
     s[ST_MINEIG_OK] = (s[ST_MINEIG] >= -tol2) ? 1.0 : 0.0;
   }
@@ -2246,27 +2193,13 @@ struct MachineT {
     }
     bsum<2>(R, pp);
     double pred = (0.0 - 0.5 * pp[0]) - pp[1];
-    const double red_reg = fmax(1.0, fabs(lb_c)) * 2.220446049250313e-16 * P.opt.reduction_regularization;
+    const double red_reg = rules::red_reg(lb_c, P.opt);
     ared = ared + red_reg;
     pred = pred + red_reg;
     const double ratio = ared / pred;
-    const double Delta = s[ST_DELTA];
-    double Dn;
-    int ru;
-    if (ared < 0.25 * pred) {
-      ru = RIPTRM_RU_REDUCED;
-      Dn = 0.25 * Delta;
-    } else if (ared >= 0.75 * pred && fabs(s[ST_NORMDX] - Delta) <= 1e-15) {
-      ru = RIPTRM_RU_EXPANDED;
-      const double d2 = 2.0 * Delta;
-      Dn = d2 < P.opt.maximal_tr_radius ? d2 : P.opt.maximal_tr_radius;
-    } else {
-      ru = RIPTRM_RU_UNCHANGED;
-      Dn = Delta;
-    }
-    if (ared > P.opt.rho * pred) {
-      const double cl = P.opt.const_left, cr = P.opt.const_right;
-      const double iright = np_max(cr, cr / mu);   // RIPTRM.py:682 (3-arg np.maximum quirk)
+    const rules::Radius ra = rules::radius_update(ared, pred, s[ST_NORMDX], s[ST_DELTA], P.opt);
+    if (rules::accepted(ared, pred, P.opt)) {
+      const double iright = rules::clip_right(mu, P.opt);
       double* Xw = V(V_X);
       double* Yw = V(V_Y);
       double* SXw = V(V_SX);
@@ -2274,19 +2207,18 @@ struct MachineT {
       #pragma unroll 4
       for (int i = tid; i < n; i += ST_THREADS) {
         const double xn = XN[i], yn = YN[i];
-        const double il = cl * np_min(np_min(Yw[i], mu / xn), 1.0);
-        const double yc = np_min(np_max(yn, il), iright);
+        const double yc = rules::clip_dual(Yw[i], yn, xn, mu, iright, P.opt);
         nd[0] += (yc != yn) ? 1.0 : 0.0;
         Xw[i] = xn;
         Yw[i] = yc;
         SXw[i] = SXN[i];
       }
       bsum<1>(R, nd);
-      set_info(RIPTRM_IS_SUCCESSFUL, true, ratio, ru, nd[0] > 0.0 ? 1.0 : 0.0);
+      set_info(RIPTRM_IS_SUCCESSFUL, true, ratio, ra.ru, nd[0] > 0.0 ? 1.0 : 0.0);
     } else {
-      set_info(RIPTRM_IS_UNSUCCESSFUL, true, ratio, ru, -1.0);
+      set_info(RIPTRM_IS_UNSUCCESSFUL, true, ratio, ra.ru, -1.0);
     }
-    s[ST_DELTA] = Dn;
+    s[ST_DELTA] = ra.Dn;
     return inner_loop_tail(false);
   }
 
@@ -2301,19 +2233,9 @@ struct MachineT {
     }
     copy(V_XPREV, V_X);
     bool exitflag = converged;
-    double rt, lim;
-    if (P.opt.inner_maxtime < 0.0) {
-      lim = P.opt.maxtime;
-      rt = (tn - s[ST_T_START]) / P.clock_hz;
-    } else {
-      lim = P.opt.inner_maxtime;
-      rt = (tn - s[ST_T_INNER]) / P.clock_hz;
-    }
-    bool reset = false;
-    if (rt >= lim) reset = true;
-    if (P.opt.inner_maxiter >= 0 && s[ST_INNER_IT] >= (double)P.opt.inner_maxiter) reset = true;
-    if (reset) {
-      cset(ST_I_STATUS, s[ST_INNER_IT] * 0.0 + (rt >= lim && !(P.opt.inner_maxiter >= 0 && s[ST_INNER_IT] >= (double)P.opt.inner_maxiter) ? RIPTRM_IS_MAX_TIME_EXCEEDED : RIPTRM_IS_MAX_ITER_EXCEEDED));
+    const int limit = rules::inner_limit(tn, s[ST_T_START], s[ST_T_INNER], P.clock_hz, s[ST_INNER_IT], P.opt);
+    if (limit != 0) {
+      cset(ST_I_STATUS, (double)limit);
       exitflag = true;
       copy(V_X, V_X0);
       copy(V_Y, V_Y0);
@@ -2323,10 +2245,8 @@ struct MachineT {
     }
     if (!exitflag) return inner_step_begin();
     // outer_step tail: RIPTRM.py:889-896
-    s[ST_MU_IDX] += 1.0;
+    rules::outer_tail(s[ST_MU_IDX], s[ST_DELTA], P.opt);
     s[ST_MU] = mu_at((int)s[ST_MU_IDX]);
-    const double mn = P.opt.minimal_initial_tr_radius;
-    s[ST_DELTA] = s[ST_DELTA] > mn ? s[ST_DELTA] : mn;
     return outer_top();
   }
 

@@ -28,6 +28,7 @@
 #include <string>
 #include <vector>
 #include "riptrm_ctx.h"
+#include "riptrm_rules.h"
 #include "riptrm_wave.h"
 #include "riptrm_trs.h"
 
@@ -35,8 +36,8 @@ namespace riptrm_si {
 
 #pragma clang fp contract(off)
 
-using riptrm::np_max;
-using riptrm::np_min;
+namespace rules = riptrm::rules;
+using rules::Info;
 using riptrm::round_up;
 
 constexpr int W = 64;
@@ -174,10 +175,6 @@ __device__ __forceinline__ PV pv_add(PV a, PV b) { return PV{a.j + b.j, a.r + b.
 __device__ __forceinline__ PV pv_sub(PV a, PV b) { return PV{a.j - b.j, a.r - b.r, a.q - b.q}; }
 __device__ __forceinline__ PV pv_scale(double s, PV a) { return PV{s * a.j, s * a.r, s * a.q}; }
 __device__ __forceinline__ PV pv_neg(PV a) { return PV{-a.j, -a.r, -a.q}; }
-
-struct Info {  // inner-iteration record of solver_status (RIPTRM.py:986-1023)
-  double has, num, status, tr, dxtype, normdx, minx, miny, compl_, hasratio, ratio, ru, dc, hasmin, mineig;
-};
 
 // ---- serial d x d linear algebra on ONE lane, register arrays, fully unrolled for D ---------
 // (numpy.linalg.solve / inv, cholesky and eigvalsh analogues; evaluation-only except inv)
@@ -888,8 +885,6 @@ struct Eng {
 
   // ---- tCG, RIPTRM.py:41-216 (eta0 = 0, identity preconditioner) ----------------------------
   __device__ __forceinline__ int tcg(const AtX& a, double Delta, PV& eta, PV& Heta, int& jout, double& hvps) {
-    const double theta = P.opt.tcg_theta, kappa = P.opt.tcg_kappa;
-    const int mininner = P.opt.tcg_mininner;
     const int maxinner = P.d * (P.d - 1) / 2 + P.d * (P.d + 1);  // manifold.dim
     eta = PV{0.0, 0.0, 0.0};
     Heta = PV{0.0, 0.0, 0.0};
@@ -906,28 +901,23 @@ struct Eng {
     double model = 0.0;
     int stop = RIPTRM_TCG_MAX_INNER_ITER;
     int j = 0;
+    const double nr0t = pow(norm_r0, P.opt.tcg_theta);   // constant over the run
     for (j = 0; j < maxinner; ++j) {
       const double th0 = tick();
       const PV Hd = hw(a, delta);
       pt[RIPTRM_SI_PROF_HVP] += tick() - th0;
       hvps += 1.0;
-      const double d_Hd = inner(a.g, delta, Hd);
-      double alpha = 0.0, e_Pe_new;
-      if (d_Hd != 0.0) {
-        alpha = z_r / d_Hd;
-        e_Pe_new = (e_Pe + 2.0 * alpha * e_Pd) + (alpha * alpha) * d_Pd;
-      } else {
-        e_Pe_new = e_Pe;
-      }
-      const double D2 = Delta * Delta;
-      if (d_Hd <= 0.0 || e_Pe_new >= D2) {
-        const double tau = (-e_Pd + sqrt(e_Pd * e_Pd + d_Pd * (D2 - e_Pe))) / d_Pd;
-        eta = pv_add(eta, pv_scale(tau, delta));
-        Heta = pv_add(Heta, pv_scale(tau, Hd));
-        stop = d_Hd <= 0.0 ? RIPTRM_TCG_NEGATIVE_CURVATURE : RIPTRM_TCG_EXCEEDED_TR;
+      const double d_Hd = inner(a.g, delta, Hd);   // no non-finite guard in this engine (riptrm_rules.h)
+      const rules::Curvature cv = rules::tcg_curvature(d_Hd, z_r, e_Pd, d_Pd, e_Pe, Delta);
+      const double alpha = cv.alpha;
+      if (cv.boundary) {
+        const rules::Boundary bd = rules::tcg_boundary(d_Hd, e_Pd, d_Pd, e_Pe, Delta);
+        eta = pv_add(eta, pv_scale(bd.tau, delta));
+        Heta = pv_add(Heta, pv_scale(bd.tau, Hd));
+        stop = bd.stop;
         break;
       }
-      e_Pe = e_Pe_new;
+      e_Pe = cv.e_Pe_new;
       const PV ne = pv_add(eta, pv_scale(alpha, delta));
       const PV nh = pv_add(Heta, pv_scale(alpha, Hd));
       const double nm = inner(a.g, ne, a.c) + 0.5 * inner(a.g, ne, nh);
@@ -941,20 +931,22 @@ struct Eng {
       r = pv_add(r, pv_scale(alpha, Hd));
       r_r = inner(a.g, r, r);
       norm_r = sqrt(r_r);
-      if (j >= mininner && norm_r <= norm_r0 * fmin(pow(norm_r0, theta), kappa)) {
-        stop = kappa < pow(norm_r0, theta) ? RIPTRM_TCG_REACHED_TARGET_LINEAR : RIPTRM_TCG_REACHED_TARGET_SUPERLINEAR;
+      const int target = rules::tcg_target((double)j, P.opt.tcg_mininner, norm_r, norm_r0, nr0t, P.opt.tcg_kappa);
+      if (target != rules::TCG_CONTINUE) {
+        stop = target;
         break;
       }
       z = r;
-      const double zold = z_r;
-      z_r = r_r;   // inner(z, r) with z = r: pymanopt reuses solve(x, r) for both operands -> == r_r
-      const double beta = z_r / zold;
+      // inner(z, r) with z = r: pymanopt reuses solve(x, r) for both operands -> == r_r
+      const double beta = rules::tcg_beta(r_r, z_r);
       delta = pv_add(pv_neg(z), pv_scale(beta, delta));
       delta = proj(delta);
-      e_Pd = beta * (e_Pd + alpha * d_Pd);
-      d_Pd = z_r + (beta * beta) * d_Pd;
+      const rules::Advance av = rules::tcg_advance((double)j, maxinner, beta, r_r, e_Pd, d_Pd, alpha);
+      z_r = av.z_r;
+      e_Pd = av.e_Pd;
+      d_Pd = av.d_Pd;
+      if (av.stop != rules::TCG_CONTINUE) break;   // stop is RIPTRM_TCG_MAX_INNER_ITER already; j stays
     }
-    if (j >= maxinner) j = maxinner - 1;  // Python's range loop variable after exhaustion
     jout = j;
     return stop;
   }
@@ -1224,47 +1216,16 @@ struct Eng {
     return rmax(t);
   }
 
-  __device__ __forceinline__ void log_row(const double (&ev)[10], double outer_it, double mu, const Info* inf, double tcg_iters,
-                          double t_now, double t_start, double& count, double& overflow) {
+  __device__ __forceinline__ void log_row(const double (&ev)[10], double outer_it, double mu, const Info& inf, bool has_info,
+                                          double tcg_iters, double t_now, double t_start, double& count, double& overflow) {
     if (l == 0) {
       const int cnt = (int)count;
       const int64_t capl = P.opt.log_capacity < P.cap ? P.opt.log_capacity : P.cap;
       if (capl > 0) {
         if (cnt >= capl) overflow += 1.0;   // a record leaves the middle of the log (head + latest kept)
         double* L = P.log + ((int64_t)b * P.cap + riptrm::log_slot(cnt, capl)) * RIPTRM_LOG_NFIELDS;
-        for (int k = 0; k < RIPTRM_LOG_NFIELDS; ++k) L[k] = 0.0;
-        L[RIPTRM_LOG_ITERATION] = outer_it;
-        L[RIPTRM_LOG_TIME] = (cnt == 0) ? 0.0 : (t_now - t_start) / P.clock_hz;
-        L[RIPTRM_LOG_COST] = ev[0];
-        L[RIPTRM_LOG_DISTANCE] = ev[1];
-        L[RIPTRM_LOG_RESIDUAL] = ev[2];
-        L[RIPTRM_LOG_GRADNORM] = ev[3];
-        L[RIPTRM_LOG_COMPLVIOLATION] = ev[4];
-        L[RIPTRM_LOG_DUALVIOLATION] = ev[5];
-        L[RIPTRM_LOG_MANVIOLATION] = ev[6];
-        L[RIPTRM_LOG_MAXVIOLATION] = ev[7];
-        L[RIPTRM_LOG_MEANVIOLATION] = ev[8];
-        L[RIPTRM_LOG_MU] = mu;
-        L[RIPTRM_LOG_MAXABSLAGMULT] = ev[9];
-        L[RIPTRM_LOG_TCG_ITERS] = tcg_iters;
-        L[RIPTRM_LOG_DUAL_CLIPPING] = -1.0;
-        if (inf) {
-          L[RIPTRM_LOG_HAS_INFO] = inf->has;
-          L[RIPTRM_LOG_NUM_INNER] = inf->num;
-          L[RIPTRM_LOG_INNER_STATUS] = inf->status;
-          L[RIPTRM_LOG_TR_RADIUS] = inf->tr;
-          L[RIPTRM_LOG_DXTYPE] = inf->dxtype;
-          L[RIPTRM_LOG_NORMDX] = inf->normdx;
-          L[RIPTRM_LOG_MINXFEASI] = inf->minx;
-          L[RIPTRM_LOG_MINYFEASI] = inf->miny;
-          L[RIPTRM_LOG_COMPL] = inf->compl_;
-          L[RIPTRM_LOG_HAS_RATIO] = inf->hasratio;
-          L[RIPTRM_LOG_ARED_PRED] = inf->ratio;
-          L[RIPTRM_LOG_RADIUS_UPDATE] = inf->ru;
-          L[RIPTRM_LOG_DUAL_CLIPPING] = inf->dc;
-          L[RIPTRM_LOG_HAS_MINEIG] = inf->hasmin;
-          L[RIPTRM_LOG_MINEIGVALHW] = inf->mineig;
-        }
+        rules::write_log_row(L, rules::ROW_BLANK, outer_it, rules::log_time(cnt == 0, t_now, t_start, P.clock_hz), ev, mu,
+                             tcg_iters, inf, has_info, true);
       } else {
         overflow += 1.0;
       }
@@ -1283,10 +1244,7 @@ struct Eng {
       base[2 * dd + l] = v.q;
     }
   }
-  __device__ __forceinline__ double mu_at(int idx) const {
-    const int i = idx < P.tab_len ? idx : P.tab_len - 1;
-    return P.mu_tab[i];
-  }
+  __device__ __forceinline__ double mu_at(int idx) const { return P.mu_tab[rules::tab_index(idx, P.tab_len)]; }
 
   // ---- the whole run: RIPTRM.run / outer_step / inner_run / inner_step ----------------------
   // resume = false: a new solve from P.in_x / P.in_y.  resume = true (HBM subproblem path only): an
@@ -1359,23 +1317,18 @@ struct Eng {
       evaluation(xHead, x, y, ev);
       tn = now();
       if (outer_it == 0.0 || !save_inner)
-        log_row(ev, outer_it, mu, (outer_it != 0.0 && have_info) ? &info : nullptr, last_j + 1.0, tn, t_start,
-                log_count, log_over);
+        log_row(ev, outer_it, mu, info, outer_it != 0.0 && have_info, last_j + 1.0, tn, t_start, log_count, log_over);
       residual = ev[2];
       xHead = x;
       const double rt = (tn - t_start) / P.clock_hz;
-      int stop = RIPTRM_STOP_NONE;
-      if (rt >= P.opt.maxtime) stop = RIPTRM_STOP_MAXTIME;
-      else if (outer_it >= (double)P.opt.maxiter) stop = RIPTRM_STOP_MAXITER;
-      if (ev[2] <= P.opt.tolresid) stop = RIPTRM_STOP_TOLRESID;
+      const int stop = rules::outer_stop(rt, outer_it, ev[2], P.opt);
       if (stop != RIPTRM_STOP_NONE) {
         stop_code = stop;
         stop_rt = rt;
         break;
       }
       // restart_every cycling (benchmark windows)
-      const int k = P.opt.restart_every;
-      if (k > 0 && outer_it > 0.0 && fmod(outer_it, (double)k) == 0.0) {
+      if (rules::restart_due(outer_it, P.opt)) {
         x = xI;
         y = yI;
         xPrev = x;
@@ -1391,7 +1344,7 @@ struct Eng {
       inner_it = 0.0;
       t_inner = now();
      }
-      const int ti = (int)mu_idx < P.tab_len ? (int)mu_idx : P.tab_len - 1;
+      const int ti = rules::tab_index((int)mu_idx, P.tab_len);
       const double tolL = P.tolL_tab[ti], tolC = P.tolC_tab[ti];
       while (true) {  // inner_run, RIPTRM.py:785-847
         if (rph == 0) inner_it += 1.0;
@@ -1471,8 +1424,7 @@ struct Eng {
           } else {
             me = mineig_at(xN, yN, mu, hvps);
           }
-          const double tol2 = P.opt.tol2_table ? P.opt.tol2_table[ti] : mu;
-          mineig_ok = me >= -tol2;
+          mineig_ok = me >= -rules::tol2(P.opt, ti, mu);
           info.hasmin = 1.0;
           info.mineig = me;
         }
@@ -1499,34 +1451,16 @@ struct Eng {
           const PV Hdx = hw(a, eta);
           hvps += 1.0;
           double pred = (0.0 - 0.5 * inner(a.g, Hdx, eta)) - inner(a.g, a.c, eta);
-          const double red_reg = fmax(1.0, fabs(lb_c)) * 2.220446049250313e-16 * P.opt.reduction_regularization;
+          const double red_reg = rules::red_reg(lb_c, P.opt);
           ared = ared + red_reg;
           pred = pred + red_reg;
-          const double ratio = ared / pred;
-          double Dn;
-          int ru;
-          if (ared < 0.25 * pred) {
-            ru = RIPTRM_RU_REDUCED;
-            Dn = 0.25 * Delta;
-          } else if (ared >= 0.75 * pred && fabs(normdx - Delta) <= 1e-15) {
-            ru = RIPTRM_RU_EXPANDED;
-            const double d2 = 2.0 * Delta;
-            Dn = d2 < P.opt.maximal_tr_radius ? d2 : P.opt.maximal_tr_radius;
-          } else {
-            ru = RIPTRM_RU_UNCHANGED;
-            Dn = Delta;
-          }
+          const rules::Radius ra = rules::radius_update(ared, pred, normdx, Delta, P.opt);
           info.hasratio = 1.0;
-          info.ratio = ratio;
-          info.ru = ru;
-          if (ared > P.opt.rho * pred) {
-            const double cl = P.opt.const_left, crr = P.opt.const_right;
-            const double iright = np_max(crr, crr / mu);   // RIPTRM.py:682 (3-arg np.maximum quirk)
-            double yc = 0.0;
-            if (cact) {
-              const double il = cl * np_min(np_min(y, mu / sN), 1.0);
-              yc = np_min(np_max(yN, il), iright);
-            }
+          info.ratio = ared / pred;
+          info.ru = ra.ru;
+          if (rules::accepted(ared, pred, P.opt)) {
+            const double iright = rules::clip_right(mu, P.opt);
+            const double yc = cact ? rules::clip_dual(y, yN, sN, mu, iright, P.opt) : 0.0;
             const double nd = rsum((cact && yc != yN) ? 1.0 : 0.0);
             x = xN;
             y = yc;
@@ -1535,7 +1469,7 @@ struct Eng {
           } else {
             info.status = RIPTRM_IS_UNSUCCESSFUL;
           }
-          Delta = Dn;
+          Delta = ra.Dn;
         }
         // inner_run tail, RIPTRM.py:810-847
         pt[RIPTRM_SI_PROF_TRIAL] += tick() - tq;
@@ -1544,23 +1478,14 @@ struct Eng {
         tn = now();
         if (save_inner) {
           evaluation(xPrev, x, y, ev);
-          log_row(ev, outer_it, mu, &info, last_j + 1.0, tn, t_start, log_count, log_over);
+          log_row(ev, outer_it, mu, info, true, last_j + 1.0, tn, t_start, log_count, log_over);
         }
         pt[RIPTRM_SI_PROF_EVAL] += tick() - tq;
         xPrev = x;
         bool exitflag = converged;
-        double rti, lim;
-        if (P.opt.inner_maxtime < 0.0) {
-          lim = P.opt.maxtime;
-          rti = (tn - t_start) / P.clock_hz;
-        } else {
-          lim = P.opt.inner_maxtime;
-          rti = (tn - t_inner) / P.clock_hz;
-        }
-        const bool tmo = rti >= lim;
-        const bool imax = P.opt.inner_maxiter >= 0 && inner_it >= (double)P.opt.inner_maxiter;
-        if (tmo || imax) {
-          info.status = imax ? RIPTRM_IS_MAX_ITER_EXCEEDED : RIPTRM_IS_MAX_TIME_EXCEEDED;
+        const int limit = rules::inner_limit(tn, t_start, t_inner, P.clock_hz, inner_it, P.opt);
+        if (limit != 0) {
+          info.status = limit;
           exitflag = true;
           x = x0;
           y = y0;
@@ -1576,31 +1501,16 @@ struct Eng {
         break;
       }
       // outer_step tail, RIPTRM.py:889-896
-      mu_idx += 1.0;
+      rules::outer_tail(mu_idx, Delta, P.opt);
       mu = mu_at((int)mu_idx);
-      const double mn = P.opt.minimal_initial_tr_radius;
-      Delta = Delta > mn ? Delta : mn;
     }
     store_pv(P.x + b * v3, x);
     if (cact) P.y[(int64_t)b * m + l] = y;
     if (l == 0) {
-      double* o = P.stats + (int64_t)b * RIPTRM_STAT_NFIELDS;
-      for (int k = 0; k < RIPTRM_STAT_NFIELDS; ++k) o[k] = 0.0;
-      o[RIPTRM_STAT_OUTER_ITERS] = outer_it;
-      o[RIPTRM_STAT_INNER_ITERS] = inner_total;
-      o[RIPTRM_STAT_TCG_ITERS] = tcg_total;
-      o[RIPTRM_STAT_PASSES] = hvps;
-      o[RIPTRM_STAT_STOP_CODE] = stop_code;
-      o[RIPTRM_STAT_STOP_RUNTIME] = stop_rt;
-      o[RIPTRM_STAT_FINAL_RESIDUAL] = residual;
-      o[RIPTRM_STAT_LOG_COUNT] = log_count;
-      o[RIPTRM_STAT_LOG_OVERFLOW] = log_over;
-      o[RIPTRM_STAT_PHASE] = err != RIPTRM_ERR_NONE ? riptrm::PH_ERROR : riptrm::PH_DONE;
-      o[RIPTRM_STAT_ERROR] = err;
-      o[RIPTRM_STAT_MU] = mu;
-      o[RIPTRM_STAT_TR_RADIUS] = Delta;
-      o[RIPTRM_STAT_TCG_LAST_J] = last_j;
-      o[RIPTRM_STAT_TCG_LAST_STOP] = last_stop;
+      const double phase = err != RIPTRM_ERR_NONE ? riptrm::PH_ERROR : riptrm::PH_DONE;
+      rules::write_stats(P.stats + (int64_t)b * RIPTRM_STAT_NFIELDS, true,
+                         rules::Stats{outer_it, inner_total, tcg_total, hvps, stop_code, stop_rt, residual, log_count,
+                                      log_over, phase, (double)err, mu, Delta, last_j, last_stop});
       if (P.prof) {
         pt[RIPTRM_SI_PROF_TOTAL] = (double)wall_clock64() - t_tick0;
         for (int k = 0; k < RIPTRM_SI_PROF_NFIELDS; ++k) P.prof[(int64_t)b * RIPTRM_SI_PROF_NFIELDS + k] = pt[k];

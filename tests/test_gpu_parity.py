@@ -88,16 +88,12 @@ def test_barrier_hessian_matches_oracle(n, B, layout):
         assert err < 1e-12, (b, err)
 
 
-@pytest.mark.parametrize("n", [50, 200, 1000])
-def test_tcg_matches_oracle_teacher_forced(n):
-    """Same (x, y, mu, Delta) in -> same tCG exit (stop reason, j) and eta."""
-    B = 6
+def _check_tcg_teacher_forced(n, mus, deltas):
+    B = len(mus)
     Zs, xs, ys = [], [], []
     for b in range(B):
         Z, x0, y0 = G.generate_instance(n, 40 + b)
         Zs.append(Z); xs.append(x0); ys.append(y0)
-    mus = np.array([0.1, 0.05, 1e-2, 1e-3, 0.1, 0.02])
-    deltas = np.array([np.pi / 8, 1e-3, 0.05, 0.3, 5.0, 0.01])
     eng = _engine(np.stack(Zs))
     eta, heta, js, stops = eng.tcg(np.stack(xs), np.stack(ys), mus, deltas)
     eta = eta.cpu().numpy()
@@ -110,6 +106,21 @@ def test_tcg_matches_oracle_teacher_forced(n):
         assert js[b] == j, (b, js[b], j)
         assert np.linalg.norm(eta[b] - e) <= 1e-9 * max(np.linalg.norm(e), 1e-300), b
         assert np.linalg.norm(heta[b] - he) <= 1e-8 * max(np.linalg.norm(he), 1e-300), b
+
+
+@pytest.mark.parametrize("n", [50, 200, 1000])
+def test_tcg_matches_oracle_teacher_forced(n):
+    """Same (x, y, mu, Delta) in -> same tCG exit (stop reason, j) and eta."""
+    _check_tcg_teacher_forced(n, np.array([0.1, 0.05, 1e-2, 1e-3, 0.1, 0.02]),
+                              np.array([np.pi / 8, 1e-3, 0.05, 0.3, 5.0, 0.01]))
+
+
+def test_tcg_matches_oracle_teacher_forced_memory_path():
+    """n = 4097 is the smallest n whose tCG iterations run on the workspace-memory path (above the
+    register-resident limit of 8 elements x 512 threads).  The oracle stops instance 0 at the
+    boundary (EXCEEDED_TR, j = 2), instance 1 at the target (REACHED_TARGET_LINEAR, j = 6) and
+    instance 2 at the boundary at once (EXCEEDED_TR, j = 0)."""
+    _check_tcg_teacher_forced(4097, np.array([0.1, 1e-3, 1e-2]), np.array([np.pi / 8, 5.0, 1e-3]))
 
 
 def _compare_logs(gl, rl):
